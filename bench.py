@@ -13,8 +13,13 @@ PyrLK (win 21) over every track's corners, per-track similarity fit (KLT box
 propagation), and the native cv::tbd::Tracker step on the frame's
 ground-truth detections.
 
-Secondary objects (never `value`): the whole sequence in steady state, median
-of 5 runs (`sequence`); the same frames uploaded from pinned host memory
+A plain run (`bench.py --gpus 1 --steps K --warmup W`) renders the sequence,
+warms up, times the K steps, writes their outputs when --dump-outputs DIR is
+given (dump_outputs) and prints the line.  Every other leg runs only with
+--full, after the timed steps.
+
+Secondary objects (--full; never `value`): the whole sequence in steady state,
+median of 5 runs (`sequence`); the same frames uploaded from pinned host memory
 (`with_h2d`); KITTI-shaped configs[3] (`kitti`); per-frame API (`step_api`);
 dense Farneback and the fp16 pixel path (configs[4]); the HOG detector.
 
@@ -22,7 +27,8 @@ Multi-GPU: one process per GPU (torchrun), one independent sequence per GPU
 (seed + rank), no data-path collective; value = frames of all ranks / max
 wall time over ranks ("scaling": "weak").
 
-Prints ONE JSON line on rank 0 (contract in the task description), including
+Prints ONE JSON line on rank 0 (metric, value, unit, higher_is_better, dtype,
+ms_per_step: the milliseconds one timed step took); with --full it includes
 "roofline" for the dominant kernel (lk_sparse, VALU-bound -> TFLOP/s against
 the 157.3 TF f32 peak) and "cpu_baseline" (the CPU oracle restatement of the
 same per-frame KLT work, timed on this host).
@@ -1094,6 +1100,32 @@ class TbdMeasure:
         return out
 
 
+# the FrameMetrics fields that are results (the host_*_us times and the early-GFTT count say how a
+# step ran, not what it computed)
+DUMP_METRIC_FIELDS = ("tp", "fn", "fp", "gt", "matches", "bbox_overlap", "ntracks", "lk_points", "klt_points",
+                      "klt_predicted", "redetected", "lk_iters")
+
+
+def dump_outputs(dirname: str, per_step, loop) -> None:
+    """--dump-outputs: what the timed steps handed their caller, as float64 .npy
+    files (a few hundred KB; the integers fit float64 exactly):
+      frame_metrics.npy  (steps, len(DUMP_METRIC_FIELDS)): every timed step's FrameMetrics, the last row the last step's
+      tracks.npy         (ntracks, 14): tbdk_tbd_tracks after the last step, the TrackInfo fields in the tracker's order
+      predictions.npy    (n, 3): (track id, cx, cy) of the KLT predictions the last step gave the tracker, by track id
+    The sequence is a function of --seed and the sizes only, so two builds run
+    with the same arguments can be compared file by file."""
+    import numpy as np
+    from opencv_amd import _lib
+
+    os.makedirs(dirname, exist_ok=True)
+    fm = np.array([[float(getattr(x, k)) for k in DUMP_METRIC_FIELDS] for x in per_step], dtype=np.float64)
+    tr = np.array([[float(v) for v in t.values()] for t in loop.tracks()], dtype=np.float64)
+    pr = np.array([[float(tid), cx, cy] for tid, (cx, cy) in sorted(loop.predictions().items())], dtype=np.float64)
+    np.save(os.path.join(dirname, "frame_metrics.npy"), fm.reshape(len(per_step), len(DUMP_METRIC_FIELDS)))
+    np.save(os.path.join(dirname, "tracks.npy"), tr.reshape(-1, len(_lib.TrackInfo._fields_)))
+    np.save(os.path.join(dirname, "predictions.npy"), pr.reshape(-1, 3))
+
+
 def timed_on_all_ranks(fn, world):
     """Barrier + sync, fn(), sync, barrier; the max wall time over ranks."""
     import torch
@@ -1511,6 +1543,13 @@ def main(argv=None):
     ap.add_argument("--hog-width", type=int, default=1920)
     ap.add_argument("--hog-height", type=int, default=1080)
     ap.add_argument("--hog-frames", type=int, default=60)
+    ap.add_argument("--full", action="store_true",
+                    help="after the timed steps also run every other leg (whole-sequence repeats, with-H2D, KITTI, "
+                         "the per-kernel event pass and rooflines, the secondaries, the CPU baselines; each can be "
+                         "switched off with its --no-* option).  Without it: set-up, warm-up, the timed steps, the line")
+    ap.add_argument("--dump-outputs", default=None, metavar="DIR",
+                    help="write what the timed steps returned (per-step results, the tracks and KLT predictions "
+                         "after the last step) as DIR/<name>.npy (float64)")
     ap.add_argument("--rehearse", type=float, default=None, metavar="MS_PER_STEP",
                     help="rehearse the multi-rank contract with no GPU: every step of rank r sleeps "
                          "MS_PER_STEP x (1 + r) ms (tests/test_bench_dist.py); the line says data: rehearsal")
@@ -1523,6 +1562,8 @@ def main(argv=None):
     check_world(args.gpus, world)
     if args.rehearse is not None:
         return rehearse(args, world, rank)
+    if not args.full:  # a plain run ends after the timed steps: no leg below the contract's line runs
+        args.no_cpu_baseline = True
     if args.no_secondary:
         args.no_step_api = args.no_h2d = args.no_kitti = args.no_farneback = args.no_f16 = args.no_hog = True
         args.no_dense = True
@@ -1562,6 +1603,9 @@ def main(argv=None):
     # legs measuring a cooled-down device (whole-sequence repeats ~9 % below
     # the timed region right after it)
     line, ms = run_contract(args, world, rank, m, torch.cuda.synchronize, "cpu", cpu_leg=None)
+    if args.dump_outputs and rank == 0:
+        progress("writing the timed steps' outputs")
+        dump_outputs(args.dump_outputs, ms, m.loop)
     nb = 60  # frames handed to the CPU baseline (it stops at its time budget)
     cpu_in = (m.frames[:nb].cpu().numpy(), m.gtn[:nb]) if (rank == 0 and world == 1 and
                                                           not args.no_cpu_baseline) else None
@@ -1590,6 +1634,32 @@ def main(argv=None):
     ctx.set_option("timing_every", 1)
     nolaunch = {"launches": 0, "avg_us": None, "total_ms": 0.0}
     w0, nframes = args.warmup, args.warmup + args.steps
+    nlev = args.max_level + 1
+    line.update({
+        "dtype": "u8",
+        "data": "synthetic (deterministic in-repo generator, opencv_amd/csrc/synth_spec.h)",
+        "config": {"workload": f"TBD loop {args.width}x{args.height} x {args.objects} objects "
+                               f"(BASELINE configs[2]), frames [{w0}, {nframes}) of a {m.nseq}-frame sequence "
+                               "per GPU",
+                   "levels": nlev, "win": args.win, "gftt": f"256/box, q 0.01, minDist 3, every {args.redetect}",
+                   "tracker_bounds": args.bounds, "parallelism": f"replicas x{world} (one sequence per GPU)",
+                   "api": {"run": "tbdk_tbd_run (native frame loop, look-ahead)",
+                           "ahead": "tbdk_tbd_step_ahead per frame", "step": "tbdk_tbd_step per frame"}[args.api]},
+        "host_pinning": pin,
+        "kernels": kstats,
+        "per_frame": {"lk_points": lk_pts / args.steps, "tracked_points": klt_pts / args.steps,
+                      "tracks": ntr / args.steps, "gftt_rois": redet / args.steps,
+                      "gftt_rois_early": early / args.steps,
+                      "host_wait_us": h_wait / args.steps, "host_tracker_us": h_trk / args.steps,
+                      "host_step_us": h_step / args.steps, "host_launch_us": h_launch / args.steps},
+    })
+    if not args.full:
+        if rank == 0:
+            print(json.dumps(line), flush=True)
+        if world > 1:
+            dist.barrier()
+            dist.destroy_process_group()
+        return
 
     # the whole-sequence and with-H2D legs right after the timed region: the
     # per-frame step-API pass below leaves the device in a state that measured
@@ -1636,7 +1706,6 @@ def main(argv=None):
         del loop3
 
     lk = kstats.get("lk_sparse", kstats_aside.get("lk_sparse", nolaunch))
-    nlev = args.max_level + 1
     lk_every = kstats_aside.get("lk_sparse", {}).get("avg_us")
     # the line's achieved / frac: the every-launch average (the separate pass over the same frames:
     # every PyrLK launch of the loop, ~900 at 480 frames), not the timed region's sampled events
@@ -1729,27 +1798,11 @@ def main(argv=None):
                        "(~360 flop/B vs ridge ~20), so this fraction is structurally small (DESIGN.md §3)"}
 
     line.update({
-        "dtype": "u8",
-        "data": "synthetic (deterministic in-repo generator, opencv_amd/csrc/synth_spec.h)",
-        "config": {"workload": f"TBD loop {args.width}x{args.height} x {args.objects} objects "
-                               f"(BASELINE configs[2]), frames [{w0}, {nframes}) of a {m.nseq}-frame sequence "
-                               "per GPU",
-                   "levels": nlev, "win": args.win, "gftt": f"256/box, q 0.01, minDist 3, every {args.redetect}",
-                   "tracker_bounds": args.bounds, "parallelism": f"replicas x{world} (one sequence per GPU)",
-                   "api": {"run": "tbdk_tbd_run (native frame loop, look-ahead)",
-                           "ahead": "tbdk_tbd_step_ahead per frame", "step": "tbdk_tbd_step per frame"}[args.api]},
-        "host_pinning": pin,
         "step_api": step_api,
         "roofline": roofline,
         "roofline_pyramid": roof_pyr,
         "roofline_hbm_pyr_lk": roof_pl,
-        "kernels": kstats,
         "kernels_aside": kstats_aside,
-        "per_frame": {"lk_points": lk_pts / args.steps, "tracked_points": klt_pts / args.steps,
-                      "tracks": ntr / args.steps, "gftt_rois": redet / args.steps,
-                      "gftt_rois_early": early / args.steps,
-                      "host_wait_us": h_wait / args.steps, "host_tracker_us": h_trk / args.steps,
-                      "host_step_us": h_step / args.steps, "host_launch_us": h_launch / args.steps},
     })
     del m.frames, frames, m.loop
     if not args.no_kitti:

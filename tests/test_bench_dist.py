@@ -337,6 +337,47 @@ def test_loop_traffic_fields_from_committed_loop_summary():
     assert us1 is not None and us1 > 0 and all(u[1] < g[1] for u, g in zip(used1, used))
 
 
+def test_dump_outputs_writes_the_steps_results(tmp_path):
+    """bench.dump_outputs (--dump-outputs DIR): every timed step's result counts
+    (no host times, which differ from run to run), the tracks in the tracker's
+    order and the predictions by track id, as float64 .npy files."""
+    import numpy as np
+
+    sys.path.insert(0, ROOT)
+    import bench
+    from opencv_amd import _lib
+
+    steps = []
+    for i in range(3):
+        fm = _lib.FrameMetrics()
+        fm.tp, fm.ntracks, fm.bbox_overlap, fm.lk_iters, fm.host_wait_us = i, 10 + i, 0.25 * i, (1 << 40) + i, 7.0 * i
+        steps.append(fm)
+    keys = [f[0] for f in _lib.TrackInfo._fields_]
+
+    class Loop:
+        def tracks(self):
+            return [{k: (j + 1) * (n + 1) for n, k in enumerate(keys)} for j in range(2)]
+
+        def predictions(self):
+            return {9: (1.5, 2.5), 4: (3.25, 4.0)}
+
+    d = tmp_path / "out" / "dump"
+    bench.dump_outputs(str(d), steps, Loop())
+    assert sorted(p.name for p in d.iterdir()) == ["frame_metrics.npy", "predictions.npy", "tracks.npy"]
+    fm, tr, pr = (np.load(d / n) for n in ("frame_metrics.npy", "tracks.npy", "predictions.npy"))
+    assert fm.dtype == tr.dtype == pr.dtype == np.float64
+    f = bench.DUMP_METRIC_FIELDS
+    assert fm.shape == (3, len(f)) and not any(k.startswith("host_") for k in f)
+    assert fm[:, f.index("tp")].tolist() == [0, 1, 2] and fm[:, f.index("ntracks")].tolist() == [10, 11, 12]
+    assert fm[:, f.index("bbox_overlap")].tolist() == [0.0, 0.25, 0.5]
+    assert fm[2, f.index("lk_iters")] == (1 << 40) + 2
+    assert tr.shape == (2, len(keys)) and tr[1].tolist() == [2.0 * (n + 1) for n in range(len(keys))]
+    assert pr.tolist() == [[4.0, 3.25, 4.0], [9.0, 1.5, 2.5]]
+    bench.dump_outputs(str(d), [], type("E", (), {"tracks": lambda s: [], "predictions": lambda s: {}})())
+    assert np.load(d / "frame_metrics.npy").shape == (0, len(f)) and np.load(d / "tracks.npy").shape == (0, len(keys))
+    assert np.load(d / "predictions.npy").shape == (0, 3)
+
+
 def _json_lines(out):
     import json
 

@@ -22,7 +22,6 @@ import _oracle as O
 pytestmark = pytest.mark.gpu
 
 GOLDEN = os.path.join(os.path.dirname(os.path.abspath(__file__)), "golden")
-REF_DATA = "/root/reference/samples/data"
 
 
 def klt():
@@ -41,13 +40,8 @@ def grid_points(h, w, step, margin):
 
 
 def basketball_pair():
-    p1 = os.path.join(os.path.dirname(os.path.abspath(__file__)), "golden", "basketball_pair.npz")
-    if os.path.exists(p1):
-        d = np.load(p1)
-        return d["a"], d["b"]
-    a = O.read_png_gray(os.path.join(REF_DATA, "basketball1.png"))
-    b = O.read_png_gray(os.path.join(REF_DATA, "basketball2.png"))
-    return a, b
+    d = np.load(os.path.join(GOLDEN, "basketball_pair.npz"))
+    return d["a"], d["b"]
 
 
 def test_synth_render_matches_oracle(gpu):

@@ -21,7 +21,11 @@ import pytest
 import _oracle as O
 
 GOLDEN = os.path.join(os.path.dirname(os.path.abspath(__file__)), "golden")
-REF_DATA = "/root/reference/samples/data"
+
+
+def basketball1():
+    """The reference's samples/data/basketball1.png as gray, stored in golden/basketball_pair.npz."""
+    return np.load(os.path.join(GOLDEN, "basketball_pair.npz"))["a"]
 
 
 def np_reflect101(idx, n):
@@ -85,8 +89,7 @@ def test_pyrdown_matches_reference_validator(shape):
 
 
 def test_pyramid_levels_and_borders():
-    img = O.read_png_gray(os.path.join(REF_DATA, "basketball1.png")) if os.path.exists(REF_DATA) else \
-        np.random.default_rng(0).integers(0, 256, (480, 640), dtype=np.uint8)
+    img = basketball1()
     P = O.Pyramid(img, (21, 21), 3)
     assert P.nlevels == 4  # 640x480 -> 320x240 -> 160x120 -> 80x60 (stop rule lkpyramid.cpp:782)
     cur = img
@@ -146,7 +149,7 @@ def grid_points(h, w, step, margin):
 def test_lk_recovers_known_translation(accum):
     # the acceptance rule of Video_OpticalFlowPyrLK.accuracy (test_optflowpyrlk.cpp:140-225):
     # no lost points, at most a handful of points off by > 0.3 px, max error <= 1
-    img = O.read_png_gray(os.path.join(REF_DATA, "basketball1.png"))
+    img = basketball1()
     a, b = shifted_pair(img, 5, -3)
     pts = grid_points(a.shape[0], a.shape[1], 16, 40)
     nx, st, err, it = O.lk(O.Pyramid(a), O.Pyramid(b), pts, accum=accum)

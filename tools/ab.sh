@@ -10,7 +10,7 @@ for i in $(seq 1 "$n"); do
     for spec in "$@"; do
         name=${spec%%=*}; rest=${spec#*=}; lib=${rest%%,*}; flags=""
         [ "$rest" != "$lib" ] && flags=${rest#*,} && flags=${flags//,/ }
-        TBDK_LIB=$lib timeout -k 10 200 python bench.py --no-secondary --no-cpu-baseline $flags \
+        TBDK_LIB=$lib timeout -k 10 200 python bench.py --full --no-secondary --no-cpu-baseline $flags \
             > "gpurun_out/ab_${name}_${i}.json" 2> "gpurun_out/ab_${name}_${i}.err"
         python -c "import json,sys; d=json.loads(open(sys.argv[1]).read().strip().splitlines()[-1]); print(sys.argv[2], d['value'], d['roofline']['avg_us_sampled'])" \
             "gpurun_out/ab_${name}_${i}.json" "$name"

@@ -4,7 +4,7 @@ set -euo pipefail
 root=$(pwd); out=$root/$1; ctr=$2; shift 2
 mkdir -p "$out"; cd /tmp; export TMPDIR=/tmp
 timeout -k 10 300 rocprofv3 --pmc "$ctr" --kernel-trace --output-format csv -d "$out" -o pmc \
-    -- python3 "$root/bench.py" --steps 40 --no-cpu-baseline "$@" > "$out/bench.json" 2> "$out/err.txt"
+    -- python3 "$root/bench.py" --full --steps 40 --no-cpu-baseline "$@" > "$out/bench.json" 2> "$out/err.txt"
 python3 - "$out/pmc_counter_collection.csv" <<'PY'
 import csv, collections, sys
 d = collections.defaultdict(list)
