@@ -242,6 +242,13 @@ int tbdk_ctx_set_option(tbdk_ctx* ctx, const char* name, int64_t value);
  *       the look-ahead PyrLK's completion event and then launches the fit on
  *       the step's stream behind the step's own PyrLK, instead of enqueuing a
  *       cross-stream wait in front of the fit (results equal; A/B runs).
+ *   "tbd_fit_ransac" (0..10000, default 0; taken by tbdk_tbd_create): 0: the
+ *       TBD loop fits each track's similarity to all its tracked corners
+ *       (getRTMatrix); N > 0: the fit is cv::estimateRigidTransform's, RANSAC
+ *       with ransacMaxIters = N and ransacGoodRatio = 0.5 over the same
+ *       corners (see tbdk_box_propagate_ransac); a track without consensus
+ *       gets no KLT prediction in that frame.  The tracked sets themselves
+ *       are unchanged (outlier corners are kept).
  *   "tbd_async_la" (0/1, default 0; taken by tbdk_tbd_create): the TBD loop's
  *       look-ahead PyrLK launches are issued by a worker thread of the loop
  *       (one more host thread per loop, spinning between frames; results equal;
@@ -487,6 +494,38 @@ typedef struct tbdk_box_fit {
 int tbdk_box_propagate(tbdk_ctx* ctx, const float* prev_pts, const float* next_pts, const uint8_t* status,
                        const int32_t* offsets, const tbdk_roi* boxes, int nboxes, int min_points,
                        tbdk_box_fit* out, void* stream);
+
+/* RANSAC parameters of cv::estimateRigidTransform's 6-argument overload
+ * (ransacMaxIters, ransacGoodRatio; ransacSize0 is 3). */
+typedef struct tbdk_ransac_params {
+    int32_t max_iters;               /* 1..10000, reference default 500 */
+    double good_ratio;               /* [0, 1], reference default 0.5 */
+} tbdk_ransac_params;
+int tbdk_ransac_default_params(tbdk_ransac_params* p);
+
+/* Batched cv::estimateRigidTransform(A, B, fullAffine = false) on point sets
+ * (video/src/lkpyramid.cpp:1591-1688), one box per set: the consensus set is
+ * found by the reference's RANSAC (its cv::RNG sequence, seeded per set, its
+ * redraw and abandon rules, its inlier threshold from boundingRect(next)), then
+ * getRTMatrix is fitted to the inliers and the box centre mapped through it.
+ * Arguments as tbdk_box_propagate, plus:
+ *   out[i].npoints : consensus size the final fit used (0 without consensus);
+ *                    -1 if the box has more than 1024 status != 0 pairs (the
+ *                    set is never truncated; valid = 0)
+ *   out[i].valid   : consensus found, npoints >= min_points, non-singular,
+ *                    scale in (0.5, 2), centre finite; without a transform
+ *                    valid = 0 and m is the identity
+ *   iters          : device int32 per box or NULL: the round k at which
+ *                    consensus was reached, -1 if none
+ *   inliers        : device u8 per point or NULL: 1 for consensus members, 0
+ *                    for outliers, status == 0 points and boxes without consensus
+ * The work per box is bounded by max_iters rounds of up to 2 * max_iters draws
+ * (reached by coincident or collinear sets).  TBDK_EINVAL for parameters out
+ * of range.  Timed as kernel "box_propagate_ransac". */
+int tbdk_box_propagate_ransac(tbdk_ctx* ctx, const float* prev_pts, const float* next_pts, const uint8_t* status,
+                              const int32_t* offsets, const tbdk_roi* boxes, int nboxes, int min_points,
+                              const tbdk_ransac_params* params, tbdk_box_fit* out, int32_t* iters, uint8_t* inliers,
+                              void* stream);
 
 /* ---- affine warp ------------------------------------------------------------ */
 

@@ -397,6 +397,27 @@ inline void warpAffine(Context& ctx, const GpuImage& src, GpuImage& dst, const d
           "tbdk_warp_affine_u8");
 }
 
+// cv::estimateRigidTransform(src1, src2, false, ransacMaxIters, ransacGoodRatio, 3)
+// (video/tracking.hpp) on device point sets, batched: set i is points
+// [offsets[i], offsets[i + 1]) of prevPts -> nextPts (device float2 arrays),
+// status a device u8 mask or nullptr.  out[i].m is the 2x3 transform (the
+// identity and valid = 0 where the reference returns an empty Mat), out[i].cx/cy
+// the centre of boxes[i] mapped by it; iters / inliers may be nullptr
+// (tbdk_box_propagate_ransac).
+inline void estimateRigidTransform(Context& ctx, const float* prevPts, const float* nextPts, const uint8_t* status,
+                                   const int32_t* offsets, const tbdk_roi* boxes, int nsets, tbdk_box_fit* out,
+                                   int ransacMaxIters = 500, double ransacGoodRatio = 0.5, int minPoints = 3,
+                                   int32_t* iters = nullptr, uint8_t* inliers = nullptr, void* stream = nullptr)
+{
+    tbdk_ransac_params p;
+    check(tbdk_ransac_default_params(&p), "tbdk_ransac_default_params");
+    p.max_iters = ransacMaxIters;
+    p.good_ratio = ransacGoodRatio;
+    check(tbdk_box_propagate_ransac(ctx.get(), prevPts, nextPts, status, offsets, boxes, nsets, minPoints, &p, out,
+                                    iters, inliers, stream),
+          "tbdk_box_propagate_ransac");
+}
+
 // cv::cuda::FarnebackOpticalFlow (cudaoptflow.hpp:210-252): create() with the
 // reference's defaults, the getters/setters, calc(I0, I1, flow, stream).
 // flow: device CV_32FC2 (dx, dy interleaved), flowPitch in bytes.

@@ -128,6 +128,10 @@ class BoxFit(C.Structure):
                 ("valid", C.c_int32)]
 
 
+class RansacParams(C.Structure):
+    _fields_ = [("max_iters", C.c_int32), ("good_ratio", C.c_double)]
+
+
 class TrackerArgs(C.Structure):
     _fields_ = [("cost_of_non_assignment", C.c_double), ("time_window_size", C.c_int32),
                 ("track_age_threshold", C.c_int32), ("track_visibility_threshold", C.c_double),
@@ -217,6 +221,10 @@ SIGNATURES = {
     "tbdk_gftt_reserve": (C.c_int, [C.c_void_p, C.c_int, C.c_int64]),
     "tbdk_box_propagate": (C.c_int, [C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_int,
                                      C.c_int, C.c_void_p, C.c_void_p]),
+    "tbdk_ransac_default_params": (C.c_int, [C.POINTER(RansacParams)]),
+    "tbdk_box_propagate_ransac": (C.c_int, [C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p,
+                                            C.c_int, C.c_int, C.POINTER(RansacParams), C.c_void_p, C.c_void_p,
+                                            C.c_void_p, C.c_void_p]),
     "tbdk_warp_affine_u8": (C.c_int, [C.c_void_p, C.c_void_p, C.c_int, C.c_int, C.c_int, C.c_void_p, C.c_int, C.c_int,
                                       C.c_int, C.POINTER(C.c_double), C.c_int, C.c_int, C.c_int, C.c_void_p]),
     "tbdk_tracker_default_args": (C.c_int, [C.POINTER(TrackerArgs)]),

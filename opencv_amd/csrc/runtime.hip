@@ -233,6 +233,11 @@ int tbdk_ctx_set_option(tbdk_ctx* ctx, const char* name, int64_t value)
         ctx->opt_tbd_post_direct = value != 0;
         return TBDK_OK;
     }
+    if (std::strcmp(name, "tbd_fit_ransac") == 0) {
+        if (value < 0 || value > 10000) return TBDK_EINVAL;
+        ctx->opt_tbd_fit_ransac = (int)value;
+        return TBDK_OK;
+    }
     if (std::strcmp(name, "tbd_fit_gate") == 0) {
         ctx->opt_tbd_fit_gate = value != 0;
         return TBDK_OK;
@@ -1035,6 +1040,34 @@ int tbdk_box_propagate(tbdk_ctx* ctx, const float* prev_pts, const float* next_p
     hipStream_t s = static_cast<hipStream_t>(stream);
     int rec = timing_begin(ctx, "box_propagate", s);
     hipError_t e = launch_box_propagate(prev_pts, next_pts, status, offsets, boxes, nboxes, min_points, out, s);
+    timing_end(ctx, rec, s);
+    return map_err(e);
+}
+
+int tbdk_ransac_default_params(tbdk_ransac_params* p)
+{
+    if (!p) return TBDK_EINVAL;
+    p->max_iters = 500;
+    p->good_ratio = 0.5;
+    return TBDK_OK;
+}
+
+int tbdk_box_propagate_ransac(tbdk_ctx* ctx, const float* prev_pts, const float* next_pts, const uint8_t* status,
+                              const int32_t* offsets, const tbdk_roi* boxes, int nboxes, int min_points,
+                              const tbdk_ransac_params* params, tbdk_box_fit* out, int32_t* iters, uint8_t* inliers,
+                              void* stream)
+{
+    if (!ctx || nboxes < 0 || !params) return TBDK_EINVAL;
+    // good_ratio outside [0, 1] (NaN included) is the reference's StsBadArg
+    if (params->max_iters < 1 || params->max_iters > 10000 || !(params->good_ratio >= 0.0 && params->good_ratio <= 1.0))
+        return TBDK_EINVAL;
+    if (nboxes == 0) return TBDK_OK;
+    if (!prev_pts || !next_pts || !offsets || !boxes || !out || min_points < 0) return TBDK_EINVAL;
+    DeviceGuard g(ctx->device);
+    hipStream_t s = static_cast<hipStream_t>(stream);
+    int rec = timing_begin(ctx, "box_propagate_ransac", s);
+    hipError_t e = launch_box_propagate_ransac(prev_pts, next_pts, status, offsets, boxes, nboxes, min_points,
+                                               params->max_iters, params->good_ratio, out, iters, inliers, s);
     timing_end(ctx, rec, s);
     return map_err(e);
 }

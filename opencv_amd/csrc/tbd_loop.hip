@@ -86,6 +86,12 @@ struct FitOut {
 #define TBDK_FIT_WAVES 8  // tracks (waves) per fit workgroup (tuning builds)
 #endif
 constexpr int kFitWaves = TBDK_FIT_WAVES;
+// Two instantiations: RANSAC = false is the default fit (least squares over
+// every tracked corner; ransac_iters is unused), RANSAC = true is ctx option
+// tbd_fit_ransac (estimateRigidTransform's consensus over the same corners,
+// ransac_iters rounds, ratio 0.5).  Only the fit call differs; the compaction,
+// the kept set and the publish code are shared.
+template <bool RANSAC>
 __global__ __launch_bounds__(64 * kFitWaves) void tbd_fit_kernel(const FitEntry* __restrict__ ents, int nents,
                                                                  float2* __restrict__ slot_pts,
                                                                  const float2* __restrict__ slot_next,
@@ -94,7 +100,8 @@ __global__ __launch_bounds__(64 * kFitWaves) void tbd_fit_kernel(const FitEntry*
                                                                  int32_t* __restrict__ slot_counts,
                                                                  FitOut* __restrict__ out, int min_fit,
                                                                  unsigned* __restrict__ fit_cnt, int32_t* flag, int tag,
-                                                                 int inl, const FitInline fi, int wg_pub)
+                                                                 int inl, const FitInline fi, int wg_pub,
+                                                                 int ransac_iters)
 {
     __shared__ float2 s_a[kFitWaves][kSlotPts], s_b[kFitWaves][kSlotPts];
     __shared__ FitOut s_out[kFitWaves];  // wg_pub: the workgroup's results, published by wave 0
@@ -155,7 +162,9 @@ __global__ __launch_bounds__(64 * kFitWaves) void tbd_fit_kernel(const FitEntry*
         __builtin_amdgcn_wave_barrier();
         for (int j = lane; j < m; j += 64) slot_pts[base + j] = sb[j];
         for (int off = 32; off >= 1; off >>= 1) it += __shfl_xor(it, off, 64);
-        const SimilarityFit f = wave_fit_similarity(sa, sb, m, lane);
+        SimilarityFit f;
+        if constexpr (RANSAC) f = wave_fit_ransac(sa, sb, m, lane, ransac_iters, 0.5).fit;  // ok = 0 without consensus
+        else f = wave_fit_similarity(sa, sb, m, lane);
         if (lane == 0) {
             slot_counts[E.slot] = m;
             FitOut o;
@@ -439,6 +448,7 @@ struct tbdk_tbd {
     // wave stores the frame's tag to h_flag (through its mapping d_flag) at
     // system scope; d_fitcnt counts the finished waves
     bool fit_flag = false;
+    int fit_ransac = 0;  // ctx option tbd_fit_ransac at create: RANSAC rounds of the fit, 0 = least squares
     int32_t* h_flag = nullptr;
     int32_t* d_flag = nullptr;
     unsigned* d_fitcnt = nullptr;
@@ -694,6 +704,7 @@ int tbdk_tbd_create(tbdk_ctx* ctx, const tbdk_tbd_config* cfg, tbdk_tbd** out)
     sm(reinterpret_cast<void**>(&t->d_ers), t->h_ers, sizeof(int32_t) * S);
     sm(reinterpret_cast<void**>(&t->d_etab), t->h_etab[0], kEarlySets * sizeof(GfttRoi) * S);
     t->fit_flag = t->zc && ctx->opt_tbd_fit_flag != 0;
+    t->fit_ransac = ctx->opt_tbd_fit_ransac;
     if (t->fit_flag) {
         hm(reinterpret_cast<void**>(&t->h_flag), 64);
         sm(reinterpret_cast<void**>(&t->d_flag), t->h_flag, 64);
@@ -1293,11 +1304,12 @@ int step_impl(tbdk_tbd* t, const uint8_t* frame, int pitch, int frame_id, const 
                 inl = 0;
         }
         int rec = timing_begin(t->ctx, "tbd_fit", s);
-        hipLaunchKernelGGL(tbd_fit_kernel, dim3((nents + kFitWaves - 1) / kFitWaves), dim3(64 * kFitWaves), 0, s,
+        hipLaunchKernelGGL(t->fit_ransac > 0 ? tbd_fit_kernel<true> : tbd_fit_kernel<false>,
+                           dim3((nents + kFitWaves - 1) / kFitWaves), dim3(64 * kFitWaves), 0, s,
                            t->d_ents, nents, t->slot_pts, t->slot_next,
                            t->slot_status, t->slot_iters, t->slot_counts, t->d_fit, c.min_fit_points,
                            by_flag ? t->d_fitcnt : nullptr, by_flag ? t->d_flag : nullptr, tag, inl, t->fit_inl,
-                           t->ctx->opt_tbd_fit_wgpub);
+                           t->ctx->opt_tbd_fit_wgpub, t->fit_ransac);
         timing_end(t->ctx, rec, s);
         if (!t->zc) e = hipMemcpyAsync(t->h_fit, t->d_fit, sizeof(FitOut) * nents, hipMemcpyDeviceToHost, s);
         if (e == hipSuccess && !by_flag) e = hipEventRecord(t->fit_done, s);

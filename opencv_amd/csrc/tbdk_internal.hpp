@@ -107,6 +107,7 @@ struct tbdk_ctx {
     int opt_tbd_gftt_ahead = 1;  // tbdk_ctx_set_option("tbd_gftt_ahead"): tbdk_tbd_run's early GFTT a frame ahead
     int opt_tbd_borrow_l0 = 0;   // tbdk_ctx_set_option("tbd_borrow_l0"): tbdk_tbd_run's pyramids take the frame as level 0 (A/B)
     int opt_tbd_fit_gate = 1;    // tbdk_ctx_set_option("tbd_fit_gate"): the host launches the fit once the look-ahead PyrLK is done
+    int opt_tbd_fit_ransac = 0;  // tbdk_ctx_set_option("tbd_fit_ransac"): RANSAC rounds of the loop's fit, 0 = least squares (read by tbdk_tbd_create)
     int opt_tbd_async_la = 0;    // tbdk_ctx_set_option("tbd_async_la"): look-ahead launches by a worker thread (read by tbdk_tbd_create)
     std::string timing_only;  // ",name,name," filter of tbdk_timing_select ("" = all)
     int timing_every = 1;     // tbdk_ctx_set_option("timing_every"): events on every Nth selected launch
@@ -289,6 +290,10 @@ hipError_t launch_lk_f16(const LkArgs& a, bool f32, hipStream_t s);  // fp16 or 
 // ---- box propagation (box_fit.hip) ----
 hipError_t launch_box_propagate(const float* prev, const float* next, const uint8_t* status, const int32_t* offsets,
                                 const tbdk_roi* boxes, int nboxes, int min_points, tbdk_box_fit* out, hipStream_t s);
+hipError_t launch_box_propagate_ransac(const float* prev, const float* next, const uint8_t* status,
+                                       const int32_t* offsets, const tbdk_roi* boxes, int nboxes, int min_points,
+                                       int max_iters, double good_ratio, tbdk_box_fit* out, int32_t* iters,
+                                       uint8_t* inliers, hipStream_t s);
 
 // ---- affine warp (warp.hip) ----
 void invert_affine(const double* M, double* out);

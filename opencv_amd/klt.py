@@ -304,6 +304,44 @@ def box_propagate(prev_pts: torch.Tensor, next_pts: torch.Tensor, status, offset
     return np.frombuffer(res.tobytes(), BOX_FIT_DTYPE)[:nb].copy()
 
 
+def box_propagate_ransac(prev_pts: torch.Tensor, next_pts: torch.Tensor, status, offsets: torch.Tensor,
+                          boxes: torch.Tensor, min_points: int = 4, max_iters: int | None = None,
+                          good_ratio: float | None = None, ctx: Context | None = None, stream=None):
+    """tbdk_box_propagate_ransac: cv::estimateRigidTransform(prev, next, False,
+    max_iters, good_ratio, 3) per box (the reference's RANSAC consensus, then
+    getRTMatrix over its inliers) and the box centre the transform carries.
+    Arguments as box_propagate; max_iters / good_ratio default to the
+    reference's 500 / 0.5.  Returns (fit, iters, inliers): a BOX_FIT_DTYPE array
+    (npoints = consensus size, -1 for a box of more than 1024 tracked pairs),
+    int32 per box (the round that reached consensus, -1: none) and uint8 per
+    point (1 = consensus member).  Synchronises the stream."""
+    for t in (prev_pts, next_pts, offsets, boxes) + ((status,) if status is not None else ()):
+        if not t.is_cuda or not t.is_contiguous():
+            raise _lib.TbdkError("box_propagate_ransac expects contiguous device tensors")
+    nb = boxes.shape[0]
+    if offsets.dtype != torch.int32 or boxes.dtype != torch.int32 or offsets.numel() != nb + 1:
+        raise _lib.TbdkError("offsets: int32 (nboxes + 1), boxes: int32 (nboxes, 4)")
+    ctx = ctx or Context.get(prev_pts.device.index or 0)
+    par = _lib.RansacParams()
+    _lib.check(ctx.lib.tbdk_ransac_default_params(C.byref(par)), "tbdk_ransac_default_params")
+    if max_iters is not None:
+        par.max_iters = int(max_iters)
+    if good_ratio is not None:
+        par.good_ratio = float(good_ratio)
+    npts = prev_pts.shape[0]
+    out = torch.zeros(max(1, nb) * BOX_FIT_DTYPE.itemsize, dtype=torch.uint8, device=prev_pts.device)
+    iters = torch.full((max(1, nb),), -1, dtype=torch.int32, device=prev_pts.device)
+    inl = torch.zeros(max(1, npts), dtype=torch.uint8, device=prev_pts.device)
+    ptr = lambda t: C.c_void_p(t.data_ptr()) if t is not None else None  # noqa: E731
+    _lib.check(ctx.lib.tbdk_box_propagate_ransac(ctx.handle, ptr(prev_pts), ptr(next_pts), ptr(status), ptr(offsets),
+                                                 ptr(boxes), nb, int(min_points), C.byref(par), ptr(out), ptr(iters),
+                                                 ptr(inl), _stream_ptr(stream)),
+               "tbdk_box_propagate_ransac")
+    res = out.cpu().numpy()
+    return (np.frombuffer(res.tobytes(), BOX_FIT_DTYPE)[:nb].copy(), iters.cpu().numpy()[:nb].copy(),
+            inl.cpu().numpy()[:npts].copy())
+
+
 # interpolation flags / border modes (reference values, imgproc.hpp / core/base.hpp)
 INTER_NEAREST, INTER_LINEAR, INTER_CUBIC, INTER_AREA, WARP_INVERSE_MAP = 0, 1, 2, 3, 16
 BORDER_CONSTANT, BORDER_REPLICATE, BORDER_REFLECT, BORDER_WRAP, BORDER_REFLECT_101, BORDER_TRANSPARENT = range(6)
