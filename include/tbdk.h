@@ -558,6 +558,41 @@ int tbdk_warp_affine_u8(tbdk_ctx* ctx, const uint8_t* src, int src_width, int sr
                         uint8_t* dst, int dst_width, int dst_height, int dst_pitch, const double* M,
                         int flags, int border, int border_value, void* stream);
 
+/* ---- image front end: cvtColor, resize ------------------------------------- */
+
+/* colour conversion codes: the reference's values (imgproc.hpp ColorConversionCodes) */
+#define TBDK_COLOR_BGR2BGRA 0        /* alpha 255 */
+#define TBDK_COLOR_BGR2GRAY 6
+#define TBDK_COLOR_RGB2GRAY 7
+#define TBDK_COLOR_GRAY2BGR 8
+#define TBDK_COLOR_BGRA2GRAY 10
+#define TBDK_COLOR_RGBA2GRAY 11
+
+/* Replaces cv::cuda::cvtColor(src, dst, code) (cudaimgproc.hpp) for 8-bit
+ * images and the codes above, with the bits of the CPU cv::cvtColor the sample
+ * calls (samples/gpu/tbd.cpp:573-574): gray is RGB2Gray<uchar>
+ * (imgproc/src/color_rgb.simd.hpp:647), (B*1868 + G*9617 + R*4899 + 8192) >> 14.
+ *   src, dst : device u8 images of width x height pixels (interleaved channels,
+ *              row pitch in bytes); dst must not alias src
+ * TBDK_EINVAL for any other code. */
+int tbdk_cvt_color_u8(tbdk_ctx* ctx, const uint8_t* src, int width, int height, int src_pitch, uint8_t* dst,
+                      int dst_pitch, int code, void* stream);
+/* Replaces cv::cuda::resize(src, dst, Size(dst_width, dst_height), 0, 0, INTER_LINEAR)
+ * (cudawarping.hpp) for 8-bit images of cn = 1, 3 or 4 channels, bit-exact
+ * with the CPU cv::resize of samples/gpu/tbd.cpp:578 (imgproc/src/resize.cpp:
+ * 11-bit fixed-point coefficients; both scales exactly 2 is INTER_AREA,
+ * equal sizes a copy).  The per-axis coefficient tables are made on the host
+ * and cached in the context by (source, destination) size: a repeated size
+ * allocates and uploads nothing (a new size synchronises `stream` once and
+ * uploads its tables).  dst must not alias src. */
+int tbdk_resize_linear_u8(tbdk_ctx* ctx, const uint8_t* src, int width, int height, int src_pitch, int cn,
+                          uint8_t* dst, int dst_width, int dst_height, int dst_pitch, void* stream);
+/* tbdk_cvt_color_u8 (one of the four *2GRAY codes) followed by
+ * tbdk_resize_linear_u8 of the gray image, in one pass with the same bits:
+ * every source tap is converted to gray, then interpolated. */
+int tbdk_cvt_resize_gray_u8(tbdk_ctx* ctx, const uint8_t* src, int width, int height, int src_pitch, int code,
+                            uint8_t* dst, int dst_width, int dst_height, int dst_pitch, void* stream);
+
 /* ---- dense Farneback optical flow ------------------------------------------ */
 
 /* flag value of the reference (video/include/opencv2/video/tracking.hpp:58) */
@@ -919,6 +954,81 @@ int tbdk_tbd_tracking_write(tbdk_tbd* tbd, const uint32_t* history_ages, int nag
 /* The KLT predictions the last tbdk_tbd_step handed to the tracker (one per
  * track with a valid box fit, in track order); *n = their number. */
 int tbdk_tbd_predictions(const tbdk_tbd* tbd, tbdk_prediction* out, int cap, int* n);
+
+/* ---- detection-driven step: colour frame in, HOG detections, tracks out ----
+ * The per-frame path of samples/gpu/tbd.cpp:568-622 in front of the loop:
+ * cvtColor -> optional resize -> HOG detectMultiScale -> one Detection per
+ * rect -> tbdk_tbd_step. */
+typedef struct tbdk_tbd_detector tbdk_tbd_detector;
+
+typedef struct tbdk_tbd_detect_config {
+    int32_t width, height;           /* the loop's frame size: its tbdk_tbd_config width x height */
+    int32_t src_width, src_height;   /* the colour frames handed to tbdk_tbd_step_image */
+    int32_t src_cn;                  /* 3 or 4 (alpha ignored) */
+    int32_t rgb_order;               /* 0: BGR(A) (the sample's frames), 1: RGB(A) */
+    int32_t make_gray;               /* 1: HOG runs on the gray image (the sample's default); 0: on the colour image */
+    int32_t resize;                  /* 1: resize to width x height (--resize_src); 0: the sizes must be equal */
+    int32_t confidence_mode;         /* 0: every detection's confidence is -1.0, as the sample's (tbd.cpp:619);
+                                        1: the HOG weight of the grouped rect (the sample's TODO) */
+    int32_t max_detections;          /* per frame; more is TBDK_ENOMEM */
+    tbdk_hog_params hog;
+} tbdk_tbd_detect_config;
+
+/* the sample's settings (samples/gpu/tbd.cpp:436-443: 15 levels, hit threshold
+ * 0.45, the detector's other defaults), gray, no resize, BGR frames of the
+ * loop's size, confidence -1.0, 4096 detections */
+int tbdk_tbd_detect_default_config(int width, int height, tbdk_tbd_detect_config* cfg);
+/* ctx: the context `tbd` was created on; svm: host coefficients (descriptor
+ * size, or one more for the bias), copied.  The detector owns the working
+ * images (the gray frame; with make_gray = 0 the resized colour frame too).
+ * Destroy it before the loop. */
+int tbdk_tbd_detector_create(tbdk_ctx* ctx, tbdk_tbd* tbd, const tbdk_tbd_detect_config* cfg, const float* svm,
+                             int svm_len, tbdk_tbd_detector** out);
+int tbdk_tbd_detector_destroy(tbdk_tbd_detector* det);
+/* One colour frame (device u8, src_width x src_height x src_cn, pitch bytes):
+ *   1. make_gray = 1: cvtColor(*2GRAY) -> resize (one fused pass when both apply);
+ *      make_gray = 0: the colour image is resized, HOG runs on it, and the loop's
+ *      frame is its *2GRAY conversion;
+ *   2. detectMultiScale (tbdk_hog_detect_multiscale) with cfg.hog;
+ *   3. rect i becomes {id -1, rect, confidence by mode}, in the reference's
+ *      output order: levels ascending, windows row-major within a level, then
+ *      groupRectangles' class order (track ids and assignment ties depend on it);
+ *   4. tbdk_tbd_step on the gray frame with those detections.
+ * dets_out (host, cap entries; may be NULL with cap 0) receives the detections
+ * used, *ndets their number (all of them are used even when cap is smaller).
+ * Synchronous, as HOG is. */
+int tbdk_tbd_step_image(tbdk_tbd_detector* det, const uint8_t* frame, int pitch, int frame_id,
+                        tbdk_detection* dets_out, int cap, int* ndets, tbdk_frame_metrics* metrics, void* stream);
+
+/* The sample's loop over an image sequence with no bbox file
+ * (samples/gpu/tbd.cpp:568-706 with HOG detections).  image_list_filename: a
+ * text file with one path per line (relative paths: to the list's directory)
+ * of binary PNM frames, P6 (BGR order is NOT assumed: P6 is RGB) or P5 gray,
+ * maxval 255, all of one size. */
+typedef struct tbdk_app_image_args {
+    const char* image_list_filename;
+    const char* tracking_filepath;      /* the history|object|frame|scenario output (NULL or "": none) */
+    int32_t num_tracking_frames;        /* 100 */
+    int32_t make_gray;                  /* 1 */
+    int32_t resize_src, width, height;  /* 0, 640 x 480 (--resize_src, --width, --height) */
+    int32_t confidence_mode;            /* tbdk_tbd_detect_config.confidence_mode */
+    int32_t device;                     /* 0 */
+    int32_t verbose;
+    tbdk_hog_params hog;                /* the sample's settings */
+    const float* svm;                   /* HOST detector coefficients */
+    int32_t svm_len;
+    tbdk_tracker_args tracker;          /* TbdArgs defaults; the bounds filter */
+} tbdk_app_image_args;
+
+typedef struct tbdk_app_image_result {
+    int64_t frames, detections;
+    tbdk_scenario_metrics scenario;
+} tbdk_app_image_result;
+
+int tbdk_app_image_default_args(tbdk_app_image_args* args);
+/* Every listed file is opened and its header checked before any GPU work: a
+ * missing or malformed file is TBDK_EINVAL with nothing run. */
+int tbdk_app_run_images(const tbdk_app_image_args* args, tbdk_app_image_result* result);
 
 /* ---- synthetic sequences (bench / test input) ----------------------------- */
 

@@ -3,6 +3,7 @@
 //   cv::cuda::SparsePyrLKOpticalFlow   (modules/cudaoptflow/include/opencv2/cudaoptflow.hpp:160-180)
 //   cv::cuda::CornersDetector          (modules/cudaimgproc/include/opencv2/cudaimgproc.hpp:570-604)
 //   cv::cuda::pyrDown / warpAffine     (modules/cudawarping/include/opencv2/cudawarping.hpp:126,201)
+//   cv::cuda::cvtColor / resize        (cudaimgproc.hpp, cudawarping.hpp: 8-bit, the sample's codes, INTER_LINEAR)
 // changes types, not call structure.  Differences from the reference:
 //   - images are non-owning device views (GpuImage) instead of GpuMat; the
 //     caller owns all device memory;
@@ -397,6 +398,37 @@ inline void warpAffine(Context& ctx, const GpuImage& src, GpuImage& dst, const d
           "tbdk_warp_affine_u8");
 }
 
+// cv::cuda::cvtColor(src, dst, code, dcn, stream) (cudaimgproc.hpp) for 8-bit
+// images: TBDK_COLOR_BGR2GRAY / RGB2GRAY / BGRA2GRAY / RGBA2GRAY / BGR2BGRA /
+// GRAY2BGR with the CPU cv::cvtColor's bits.  dst is the caller's image of
+// src's size and the code's channel count.
+inline void cvtColor(Context& ctx, const GpuMatView& src, GpuMatView& dst, int code, void* stream = nullptr)
+{
+    const bool gray = code == TBDK_COLOR_BGR2GRAY || code == TBDK_COLOR_RGB2GRAY || code == TBDK_COLOR_BGRA2GRAY ||
+                      code == TBDK_COLOR_RGBA2GRAY;
+    const int scn = code == TBDK_COLOR_GRAY2BGR ? 1 : (code == TBDK_COLOR_BGRA2GRAY || code == TBDK_COLOR_RGBA2GRAY) ? 4 : 3;
+    const int dcn = gray ? 1 : code == TBDK_COLOR_BGR2BGRA ? 4 : code == TBDK_COLOR_GRAY2BGR ? 3 : 0;
+    if (src.depth != DEPTH_8U || dst.depth != DEPTH_8U || dcn == 0 || src.cn != scn || dst.cn != dcn ||
+        dst.width != src.width || dst.height != src.height)
+        throw Error(TBDK_EINVAL, "cvtColor");
+    check(tbdk_cvt_color_u8(ctx.get(), static_cast<const uint8_t*>(src.data), src.width, src.height, src.pitch,
+                            static_cast<uint8_t*>(dst.data), dst.pitch, code, stream),
+          "tbdk_cvt_color_u8");
+}
+
+// cv::cuda::resize(src, dst, dsize, 0, 0, INTER_LINEAR, stream) (cudawarping.hpp)
+// for 8-bit images of 1, 3 or 4 channels with the CPU cv::resize's bits; dsize
+// is dst's size.  Only TBDK_INTER_LINEAR is built.
+inline void resize(Context& ctx, const GpuMatView& src, GpuMatView& dst, int interpolation = TBDK_INTER_LINEAR,
+                   void* stream = nullptr)
+{
+    if (interpolation != TBDK_INTER_LINEAR || src.depth != DEPTH_8U || dst.depth != DEPTH_8U || dst.cn != src.cn)
+        throw Error(TBDK_EINVAL, "resize");
+    check(tbdk_resize_linear_u8(ctx.get(), static_cast<const uint8_t*>(src.data), src.width, src.height, src.pitch,
+                                src.cn, static_cast<uint8_t*>(dst.data), dst.width, dst.height, dst.pitch, stream),
+          "tbdk_resize_linear_u8");
+}
+
 // cv::estimateRigidTransform(src1, src2, false, ransacMaxIters, ransacGoodRatio, 3)
 // (video/tracking.hpp) on device point sets, batched: set i is points
 // [offsets[i], offsets[i + 1]) of prevPts -> nextPts (device float2 arrays),
@@ -547,6 +579,8 @@ public:
         if (confidences) confidences->assign(w.begin(), w.begin() + n);
         return out;
     }
+    const tbdk_hog_params& params() const { return p_; }
+    const std::vector<float>& detector() const { return svm_; }
 
 private:
     explicit HOG(Context& ctx) : ctx_(&ctx) {}
@@ -588,9 +622,54 @@ public:
         out.resize((size_t)(n < (int)out.size() ? n : (int)out.size()));
         return out;
     }
+    tbdk_tbd* get() const { return h_; }
 
 private:
     tbdk_tbd* h_ = nullptr;
+};
+
+// The sample's whole per-frame path (samples/gpu/tbd.cpp:568-622) on a TbdLoop:
+// colour frame -> cvtColor -> optional resize -> HOG detectMultiScale -> the
+// loop (tbdk_tbd_step_image).  `loop` and `ctx` must outlive it.
+class DetectingTbd {
+public:
+    // cfg: tbdk_tbd_detect_default_config(loop width, loop height) with the
+    // source size / channels / confidence mode set; its HOG settings and the
+    // detector coefficients are taken from `hog`
+    DetectingTbd(Context& ctx, TbdLoop& loop, const cuda::HOG& hog, tbdk_tbd_detect_config cfg)
+    {
+        cfg.hog = hog.params();
+        check(tbdk_tbd_detector_create(ctx.get(), loop.get(), &cfg, hog.detector().data(), (int)hog.detector().size(),
+                                       &h_),
+              "tbdk_tbd_detector_create");
+    }
+    ~DetectingTbd() { tbdk_tbd_detector_destroy(h_); }
+    DetectingTbd(const DetectingTbd&) = delete;
+    DetectingTbd& operator=(const DetectingTbd&) = delete;
+    static tbdk_tbd_detect_config defaultConfig(int width, int height)
+    {
+        tbdk_tbd_detect_config c;
+        check(tbdk_tbd_detect_default_config(width, height, &c), "tbdk_tbd_detect_default_config");
+        return c;
+    }
+    // frame: the colour frame (cfg.src_width x src_height x src_cn); detections (optional): the ones used
+    tbdk_frame_metrics step(const GpuMatView& frame, int frameId, std::vector<tbdk_detection>* detections = nullptr,
+                            void* stream = nullptr)
+    {
+        tbdk_frame_metrics m;
+        int n = 0;
+        if (frame.depth != DEPTH_8U) throw Error(TBDK_EINVAL, "DetectingTbd::step");
+        dets_.resize(dets_.empty() ? 4096 : dets_.size());
+        check(tbdk_tbd_step_image(h_, static_cast<const uint8_t*>(frame.data), frame.pitch, frameId, dets_.data(),
+                                  (int)dets_.size(), &n, &m, stream),
+              "tbdk_tbd_step_image");
+        if (detections) detections->assign(dets_.begin(), dets_.begin() + (n < (int)dets_.size() ? n : (int)dets_.size()));
+        return m;
+    }
+
+private:
+    tbdk_tbd_detector* h_ = nullptr;
+    std::vector<tbdk_detection> dets_;
 };
 
 }  // namespace tbdk

@@ -177,6 +177,34 @@ class HogParams(C.Structure):
                 ("nlevels", C.c_int32), ("hit_threshold", C.c_double), ("win_stride_x", C.c_int32),
                 ("win_stride_y", C.c_int32), ("scale0", C.c_double), ("group_threshold", C.c_int32)]
 
+
+# cv::ColorConversionCodes of tbdk_cvt_color_u8
+COLOR_BGR2BGRA = 0
+COLOR_BGR2GRAY = 6
+COLOR_RGB2GRAY = 7
+COLOR_GRAY2BGR = 8
+COLOR_BGRA2GRAY = 10
+COLOR_RGBA2GRAY = 11
+
+
+class TbdDetectConfig(C.Structure):
+    _fields_ = [("width", C.c_int32), ("height", C.c_int32), ("src_width", C.c_int32), ("src_height", C.c_int32),
+                ("src_cn", C.c_int32), ("rgb_order", C.c_int32), ("make_gray", C.c_int32), ("resize", C.c_int32),
+                ("confidence_mode", C.c_int32), ("max_detections", C.c_int32), ("hog", HogParams)]
+
+
+class AppImageArgs(C.Structure):
+    _fields_ = [("image_list_filename", C.c_char_p), ("tracking_filepath", C.c_char_p),
+                ("num_tracking_frames", C.c_int32), ("make_gray", C.c_int32), ("resize_src", C.c_int32),
+                ("width", C.c_int32), ("height", C.c_int32), ("confidence_mode", C.c_int32), ("device", C.c_int32),
+                ("verbose", C.c_int32), ("hog", HogParams), ("svm", C.POINTER(C.c_float)), ("svm_len", C.c_int32),
+                ("tracker", TrackerArgs)]
+
+
+class AppImageResult(C.Structure):
+    _fields_ = [("frames", C.c_int64), ("detections", C.c_int64), ("scenario", ScenarioMetrics)]
+
+
 _P = C.c_void_p
 _PI = C.POINTER(C.c_int)
 
@@ -300,6 +328,18 @@ SIGNATURES = {
     "tbdk_fb_level_image": (C.c_int, [_P, _P, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, C.c_double, _P,
                                       C.c_int, _P]),
     "tbdk_fb_poly_exp": (C.c_int, [_P, _P, C.c_int, C.c_int, C.c_int, C.c_int, C.c_double, _P, C.c_int, _P]),
+    "tbdk_cvt_color_u8": (C.c_int, [_P, _P, C.c_int, C.c_int, C.c_int, _P, C.c_int, C.c_int, _P]),
+    "tbdk_resize_linear_u8": (C.c_int, [_P, _P, C.c_int, C.c_int, C.c_int, C.c_int, _P, C.c_int, C.c_int, C.c_int,
+                                        _P]),
+    "tbdk_cvt_resize_gray_u8": (C.c_int, [_P, _P, C.c_int, C.c_int, C.c_int, C.c_int, _P, C.c_int, C.c_int, C.c_int,
+                                          _P]),
+    "tbdk_tbd_detect_default_config": (C.c_int, [C.c_int, C.c_int, C.POINTER(TbdDetectConfig)]),
+    "tbdk_tbd_detector_create": (C.c_int, [_P, _P, C.POINTER(TbdDetectConfig), _P, C.c_int, C.POINTER(_P)]),
+    "tbdk_tbd_detector_destroy": (C.c_int, [_P]),
+    "tbdk_tbd_step_image": (C.c_int, [_P, _P, C.c_int, C.c_int, C.POINTER(Detection), C.c_int, _PI,
+                                      C.POINTER(FrameMetrics), _P]),
+    "tbdk_app_image_default_args": (C.c_int, [C.POINTER(AppImageArgs)]),
+    "tbdk_app_run_images": (C.c_int, [C.POINTER(AppImageArgs), C.POINTER(AppImageResult)]),
 }
 
 _lib = None

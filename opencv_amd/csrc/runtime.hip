@@ -130,6 +130,7 @@ int tbdk_ctx_destroy(tbdk_ctx* ctx)
     gftt_scratch_free(ctx->gftt);
     fb_release(ctx);
     hog_release(ctx);
+    front_release(ctx);
     if (ctx->dense_buf) (void)hipFree(ctx->dense_buf);
     if (ctx->dcase_buf) (void)hipFree(ctx->dcase_buf);
     for (hipStream_t st : {ctx->tbd_side, ctx->tbd_la, ctx->tbd_early})

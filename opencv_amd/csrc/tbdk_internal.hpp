@@ -67,6 +67,7 @@ struct GfttScratch {
     int64_t cap_resp_px = 0;
 };
 struct HogScratch;  // hog.hip
+struct FrontScratch;  // frontend.hip
 
 }  // namespace tbdk
 
@@ -133,6 +134,7 @@ struct tbdk_ctx {
     // (stream order only adds dependencies).
     std::mutex tbd_mu;
     hipStream_t tbd_side = nullptr, tbd_la = nullptr, tbd_early = nullptr;
+    tbdk::FrontScratch* front = nullptr;  // resize coefficient tables by size (frontend.hip)
 };
 
 namespace tbdk {
@@ -299,6 +301,15 @@ hipError_t launch_box_propagate_ransac(const float* prev, const float* next, con
 void invert_affine(const double* M, double* out);
 hipError_t launch_warp_affine(const uint8_t* src, int sw, int sh, int spitch, uint8_t* dst, int dw, int dh, int dpitch,
                               const double* minv, int inter, int border, int cval, hipStream_t s);
+
+// ---- image front end (frontend.hip): argument checks + launch, device already current ----
+void front_release(tbdk_ctx* ctx);
+int front_cvt_color(tbdk_ctx* ctx, const uint8_t* src, int width, int height, int src_pitch, uint8_t* dst,
+                    int dst_pitch, int code, hipStream_t s);
+int front_resize_linear(tbdk_ctx* ctx, const uint8_t* src, int width, int height, int src_pitch, int cn, uint8_t* dst,
+                        int dst_width, int dst_height, int dst_pitch, hipStream_t s);
+int front_cvt_resize_gray(tbdk_ctx* ctx, const uint8_t* src, int width, int height, int src_pitch, int code,
+                          uint8_t* dst, int dst_width, int dst_height, int dst_pitch, hipStream_t s);
 
 // ---- synthetic renderer (synth.hip) ----
 struct SynPoseDev;  // == syn_pose

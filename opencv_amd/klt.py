@@ -371,6 +371,89 @@ def warp_affine(src: torch.Tensor, M, dsize, flags: int = INTER_LINEAR, borderMo
     return dst
 
 
+# cv::ColorConversionCodes the front end knows (imgproc.hpp)
+COLOR_BGR2BGRA, COLOR_BGR2GRAY, COLOR_RGB2GRAY = _lib.COLOR_BGR2BGRA, _lib.COLOR_BGR2GRAY, _lib.COLOR_RGB2GRAY
+COLOR_GRAY2BGR, COLOR_BGRA2GRAY, COLOR_RGBA2GRAY = _lib.COLOR_GRAY2BGR, _lib.COLOR_BGRA2GRAY, _lib.COLOR_RGBA2GRAY
+# code -> (source channels, destination channels)
+_COLOR_CN = {COLOR_BGR2BGRA: (3, 4), COLOR_BGR2GRAY: (3, 1), COLOR_RGB2GRAY: (3, 1), COLOR_GRAY2BGR: (1, 3),
+             COLOR_BGRA2GRAY: (4, 1), COLOR_RGBA2GRAY: (4, 1)}
+
+
+def _image_cn(img: torch.Tensor, what: str) -> int:
+    """Channel count of a u8 device image (H, W) or (H, W, cn) with packed pixels."""
+    if img.dtype != torch.uint8 or not img.is_cuda or img.dim() not in (2, 3) or img.stride(-1) != 1:
+        raise _lib.TbdkError(f"{what} expects a uint8 device tensor (H, W) or (H, W, cn)")
+    if img.dim() == 3 and img.stride(1) != img.shape[2]:
+        raise _lib.TbdkError(f"{what}: pixels must be packed (stride(1) == channels)")
+    return 1 if img.dim() == 2 else int(img.shape[2])
+
+
+def _image_dst(dst, h: int, w: int, cn: int, device, what: str) -> torch.Tensor:
+    shape = (h, w) if cn == 1 else (h, w, cn)
+    if dst is None:
+        return torch.empty(shape, dtype=torch.uint8, device=device)
+    if tuple(dst.shape) != shape or _image_cn(dst, what) != cn or dst.device != device:
+        raise _lib.TbdkError(f"{what}: dst must be a {shape} uint8 device tensor")
+    return dst
+
+
+def cvt_color(src: torch.Tensor, code: int, dst: torch.Tensor | None = None, ctx: Context | None = None,
+              stream=None) -> torch.Tensor:
+    """cv::cuda::cvtColor(src, dst, code) for 8-bit images (cudaimgproc.hpp) with the
+    CPU cv::cvtColor's bits: COLOR_BGR2GRAY / RGB2GRAY / BGRA2GRAY / RGBA2GRAY,
+    COLOR_BGR2BGRA (alpha 255) and COLOR_GRAY2BGR.  Any other code, or a source
+    whose channel count does not fit the code, raises."""
+    cn = _image_cn(src, "cvt_color")
+    if code not in _COLOR_CN:
+        raise _lib.TbdkError(f"cvt_color: unknown colour conversion code {code}")
+    if cn != _COLOR_CN[code][0]:
+        raise _lib.TbdkError(f"cvt_color: code {code} needs {_COLOR_CN[code][0]} source channels, got {cn}")
+    ctx = ctx or Context.get(src.device.index or 0)
+    h, w = src.shape[:2]
+    dst = _image_dst(dst, h, w, _COLOR_CN[code][1], src.device, "cvt_color")
+    _lib.check(ctx.lib.tbdk_cvt_color_u8(ctx.handle, C.c_void_p(src.data_ptr()), w, h, src.stride(0),
+                                         C.c_void_p(dst.data_ptr()), dst.stride(0), int(code), _stream_ptr(stream)),
+               "tbdk_cvt_color_u8")
+    return dst
+
+
+def resize_linear(src: torch.Tensor, dsize, dst: torch.Tensor | None = None, ctx: Context | None = None,
+                  stream=None) -> torch.Tensor:
+    """cv::cuda::resize(src, dst, dsize, 0, 0, INTER_LINEAR) for 8-bit images of 1, 3 or 4
+    channels (cudawarping.hpp) with the CPU cv::resize's fixed-point bits.  dsize = (width, height)."""
+    cn = _image_cn(src, "resize_linear")
+    if cn not in (1, 3, 4):
+        raise _lib.TbdkError("resize_linear: 1, 3 or 4 channels")
+    dw, dh = int(dsize[0]), int(dsize[1])
+    if dw <= 0 or dh <= 0:
+        raise _lib.TbdkError("resize_linear: empty dsize")
+    ctx = ctx or Context.get(src.device.index or 0)
+    h, w = src.shape[:2]
+    dst = _image_dst(dst, dh, dw, cn, src.device, "resize_linear")
+    _lib.check(ctx.lib.tbdk_resize_linear_u8(ctx.handle, C.c_void_p(src.data_ptr()), w, h, src.stride(0), cn,
+                                             C.c_void_p(dst.data_ptr()), dw, dh, dst.stride(0), _stream_ptr(stream)),
+               "tbdk_resize_linear_u8")
+    return dst
+
+
+def cvt_resize_gray(src: torch.Tensor, code: int, dsize, dst: torch.Tensor | None = None,
+                    ctx: Context | None = None, stream=None) -> torch.Tensor:
+    """resize_linear(cvt_color(src, code), dsize) for a *2GRAY code in one pass (the same bits)."""
+    cn = _image_cn(src, "cvt_resize_gray")
+    if _COLOR_CN.get(code, (0, 0))[1] != 1 or _COLOR_CN[code][0] != cn:
+        raise _lib.TbdkError("cvt_resize_gray: a *2GRAY code matching the source's channels")
+    dw, dh = int(dsize[0]), int(dsize[1])
+    if dw <= 0 or dh <= 0:
+        raise _lib.TbdkError("cvt_resize_gray: empty dsize")
+    ctx = ctx or Context.get(src.device.index or 0)
+    h, w = src.shape[:2]
+    dst = _image_dst(dst, dh, dw, 1, src.device, "cvt_resize_gray")
+    _lib.check(ctx.lib.tbdk_cvt_resize_gray_u8(ctx.handle, C.c_void_p(src.data_ptr()), w, h, src.stride(0), int(code),
+                                               C.c_void_p(dst.data_ptr()), dw, dh, dst.stride(0),
+                                               _stream_ptr(stream)), "tbdk_cvt_resize_gray_u8")
+    return dst
+
+
 @dataclass
 class LkResult:
     next_pts: torch.Tensor

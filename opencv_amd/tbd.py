@@ -145,6 +145,60 @@ class TbdLoop:
             C.cast(offs.ctypes.data, C.POINTER(C.c_int32)), nf, ms, _stream_ptr(stream)), "tbdk_tbd_run_host")
         return ms[:nf]
 
+    def attach_detector(self, hog, src_size=None, src_cn: int = 3, rgb_order: bool = False, make_gray: bool = True,
+                        confidence_mode: int = 0, max_detections: int = 4096):
+        """Give the loop its own detector (tbdk_tbd_detector_create): `hog` is an
+        opencv_amd.hog.HOG with its SVM detector and detectMultiScale settings;
+        src_size = (width, height) of the colour frames step_image takes (None:
+        the loop's size; another size is resized to it, the sample's --resize_src).
+        confidence_mode 0 gives every detection the sample's -1.0, 1 the HOG weight."""
+        if hog.svm.size == 0:
+            raise _lib.TbdkError("attach_detector: hog.setSVMDetector first")
+        self.detach_detector()
+        dc = _lib.TbdDetectConfig()
+        _lib.check(self.ctx.lib.tbdk_tbd_detect_default_config(self.cfg.width, self.cfg.height, C.byref(dc)),
+                   "tbdk_tbd_detect_default_config")
+        sw, sh = (self.cfg.width, self.cfg.height) if src_size is None else (int(src_size[0]), int(src_size[1]))
+        dc.src_width, dc.src_height, dc.src_cn = sw, sh, int(src_cn)
+        dc.rgb_order, dc.make_gray = int(bool(rgb_order)), int(bool(make_gray))
+        dc.resize = int((sw, sh) != (self.cfg.width, self.cfg.height))
+        dc.confidence_mode, dc.max_detections = int(confidence_mode), int(max_detections)
+        C.memmove(C.byref(dc.hog), C.byref(hog.p), C.sizeof(_lib.HogParams))
+        h = C.c_void_p()
+        _lib.check(self.ctx.lib.tbdk_tbd_detector_create(self.ctx.handle, self.handle, C.byref(dc),
+                                                         hog.svm.ctypes.data_as(C.c_void_p), hog.svm.size, C.byref(h)),
+                   "tbdk_tbd_detector_create")
+        self._det, self._det_cfg = h, dc
+        self._det_out = np.zeros(int(max_detections), DET_DTYPE)
+
+    def detach_detector(self):
+        h = getattr(self, "_det", None)
+        if h is not None and h.value:
+            self.ctx.lib.tbdk_tbd_detector_destroy(h)
+        self._det = None
+
+    def step_image(self, frame: torch.Tensor, frame_id: int, stream=None):
+        """One colour frame through the sample's whole per-frame path
+        (tbdk_tbd_step_image): cvtColor -> resize -> HOG detectMultiScale ->
+        the loop.  frame: (H, W, 3|4) uint8 device tensor of the attached source
+        size ((H, W) for a gray source).  Returns (metrics, detections), the
+        detections (a DET_DTYPE array) in the detector's output order."""
+        if getattr(self, "_det", None) is None:
+            raise _lib.TbdkError("step_image: attach_detector first")
+        dc = self._det_cfg
+        shape = (dc.src_height, dc.src_width) if dc.src_cn == 1 else (dc.src_height, dc.src_width, dc.src_cn)
+        if (frame.dtype != torch.uint8 or not frame.is_cuda or tuple(frame.shape) != shape or frame.stride(-1) != 1
+                or (frame.dim() == 3 and frame.stride(1) != dc.src_cn)):
+            raise _lib.TbdkError(f"step_image: frame must be a {shape} uint8 device tensor with packed pixels")
+        m = _lib.FrameMetrics()
+        n = C.c_int()
+        out = self._det_out
+        _lib.check(self.ctx.lib.tbdk_tbd_step_image(
+            self._det, C.c_void_p(frame.data_ptr()), int(frame.stride(0)), int(frame_id),
+            C.cast(out.ctypes.data, C.POINTER(_lib.Detection)), len(out), C.byref(n), C.byref(m),
+            _stream_ptr(stream)), "tbdk_tbd_step_image")
+        return m, out[:n.value].copy()
+
     def set_trajectories(self, traj: "Trajectories | None"):
         """Record per-object tracking results of detections with ground-truth ids
         (tbdk_tbd_set_trajectories); keep `traj` alive while attached."""
@@ -182,6 +236,7 @@ class TbdLoop:
         h = getattr(self, "handle", None)
         if h is not None and h.value:
             try:
+                self.detach_detector()
                 self.ctx.lib.tbdk_tbd_destroy(h)
             except Exception:
                 pass
@@ -427,3 +482,36 @@ def run_app(pedestrian_bbox_filename=None, vehicle_bbox_filename=None, pedestria
     _lib.check(lib.tbdk_app_run(C.byref(a), C.byref(r)), "tbdk_app_run")
     sc = [{k: getattr(r.scenario[c], k) for k, _ in _lib.ScenarioMetrics._fields_} for c in range(2)]
     return {"frames": r.frames, "detections": r.detections, "scenario": sc}
+
+
+def run_app_images(image_list_filename, hog, tracking_filepath=None, num_tracking_frames=100, make_gray=True,
+                   resize_src=False, width=640, height=480, confidence_mode=0, device=0, verbose=False,
+                   **tracker_args):
+    """The sample's loop over an image sequence with no bbox file (tbdk_app_run_images):
+    image_list_filename lists binary PNM frames (P6 colour, RGB order, or P5 gray;
+    maxval 255), one path per line; `hog` is an opencv_amd.hog.HOG with its SVM
+    detector and settings.  Writes the sample's history|object|frame|scenario
+    output to tracking_filepath.  Returns {"frames", "detections", "scenario"}."""
+    lib = _lib.load()
+    if hog.svm.size == 0:
+        raise _lib.TbdkError("run_app_images: hog.setSVMDetector first")
+    a = _lib.AppImageArgs()
+    _lib.check(lib.tbdk_app_image_default_args(C.byref(a)), "tbdk_app_image_default_args")
+    a.image_list_filename = str(image_list_filename).encode()
+    a.tracking_filepath = str(tracking_filepath).encode() if tracking_filepath else None
+    a.num_tracking_frames = int(num_tracking_frames)
+    a.make_gray, a.resize_src = int(bool(make_gray)), int(bool(resize_src))
+    a.width, a.height = int(width), int(height)
+    a.confidence_mode, a.device, a.verbose = int(confidence_mode), int(device), int(bool(verbose))
+    C.memmove(C.byref(a.hog), C.byref(hog.p), C.sizeof(_lib.HogParams))
+    svm = np.ascontiguousarray(hog.svm, dtype=np.float32)
+    a.svm = svm.ctypes.data_as(C.POINTER(C.c_float))
+    a.svm_len = svm.size
+    for k, v in tracker_args.items():
+        if not hasattr(a.tracker, k):
+            raise _lib.TbdkError(f"unknown tracker argument {k}")
+        setattr(a.tracker, k, v)
+    r = _lib.AppImageResult()
+    _lib.check(lib.tbdk_app_run_images(C.byref(a), C.byref(r)), "tbdk_app_run_images")
+    return {"frames": r.frames, "detections": r.detections,
+            "scenario": {k: getattr(r.scenario, k) for k, _ in _lib.ScenarioMetrics._fields_}}
