@@ -716,6 +716,24 @@ int tbdk_hog_blocks(tbdk_ctx* ctx, const float* grad, int grad_pitch, const uint
  * restated natively.  Replaces the tracking section of samples/gpu/tbd.cpp:624-706. */
 typedef struct tbdk_tbd tbdk_tbd;
 
+/* Accepted ranges (tbdk_tbd_create returns TBDK_EINVAL outside them and
+ * creates nothing):
+ *   width, height          > 0
+ *   win                    3..31; odd 7..31 run the several-points-per-wave
+ *                          PyrLK kernel, the others the generic one
+ *   max_level              >= 0; levels stop early on a frame too small for
+ *                          them (cv::buildOpticalFlowPyramid's rule)
+ *   lk_iters, lk_epsilon   any; used as min(max(lk_iters, 0), 100) and
+ *                          min(max(lk_epsilon, 0), 10) (lkpyramid.cpp:1332-1339)
+ *   min_eig_threshold      any (a point whose minimum eigenvalue is below it is lost)
+ *   max_corners            1..256
+ *   quality_level          > 0, finite
+ *   min_distance           >= 0, finite
+ *   redetect_every         >= 1
+ *   min_points, min_fit_points  any (a set with fewer points left is
+ *                          refreshed / gives no prediction)
+ *   time_window_size       1..64
+ *   max_tracks             >= 1 */
 typedef struct tbdk_tbd_config {
     int32_t width, height;
     /* PyrLK (cv::calcOpticalFlowPyrLK defaults except maxLevel: "3-level" = 2) */

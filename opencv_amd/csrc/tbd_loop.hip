@@ -645,6 +645,11 @@ int tbdk_tbd_create(tbdk_ctx* ctx, const tbdk_tbd_config* cfg, tbdk_tbd** out)
         cfg->win > 31 || cfg->redetect_every <= 0 || cfg->time_window_size <= 0 ||
         cfg->time_window_size > (int)tbd::kMaxTimeWindow)
         return TBDK_EINVAL;
+    // what the first step's pyramid, GFTT or PyrLK would refuse (pyr_create,
+    // gftt_prepare, lk_internal): refused here, before anything is allocated
+    if (cfg->width <= 0 || cfg->height <= 0 || cfg->max_level < 0 || !(cfg->quality_level > 0) ||
+        !std::isfinite(cfg->quality_level) || !(cfg->min_distance >= 0) || !std::isfinite(cfg->min_distance))
+        return TBDK_EINVAL;
     tbdk_tbd* t = new (std::nothrow) tbdk_tbd();
     if (!t) return TBDK_ENOMEM;
     t->ctx = ctx;
@@ -1736,9 +1741,14 @@ int tbdk_tbd_run(tbdk_tbd* t, const uint8_t* const* frames, int pitch, int first
         if (!frames[i] || det_offsets[i + 1] < det_offsets[i] || det_offsets[i] < 0) return TBDK_EINVAL;
     if (nframes > 0 && det_offsets[nframes] > det_offsets[0] && !dets) return TBDK_EINVAL;
     // ctx option tbd_borrow_l0: the frames stay valid for the whole call, so
-    // their pyramids take them as level 0 (derivative-plane pyramids excepted)
+    // their pyramids take them as level 0 (derivative-plane pyramids excepted).
+    // Only the several-points-per-wave PyrLK kernel reads a borrowed level 0
+    // (lk_internal refuses it otherwise): a window it has no instance for, or
+    // ctx option lk_impl naming another kernel, keeps the padded copy
     hipStream_t s = static_cast<hipStream_t>(stream);
+    const int lk_impl = t->ctx->opt_lk_impl;
     t->borrow = t->ctx->opt_tbd_borrow_l0 && !t->ctx->opt_tbd_pyr_derivs && t->ctx->opt_pyr_fuse &&
+                lk_multi_supported(t->cfg.win, t->cfg.win) && (lk_impl == 0 || lk_impl == 3) &&
                 t->cfg.width >= 2 * (t->cfg.win + 2) && t->cfg.height >= 2 * (t->cfg.win + 2);
     t->ahead_any = false;
     // the caller's stream after the early GFTT work launched ahead over its frames

@@ -53,59 +53,13 @@ ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 sys.path.insert(0, os.path.join(ROOT, "oracle"))
 import tbd_loop_oracle as L  # noqa: E402
 import _loop_compare as LC  # noqa: E402
+# the frame-by-frame comparison itself (shared with tests/test_gpu_tbd_configs.py);
+# no overrides: reference bounds (0, 1280, 0, 720), the bench's options
+from _loop_pair import METRIC_KEYS, gpu_rows as _gpu_rows, run_pair  # noqa: E402
 
 pytestmark = pytest.mark.gpu
 
 SEED = 20261015
-METRIC_KEYS = ("tp", "fn", "fp", "gt", "ntracks", "lk_points", "klt_points", "klt_predicted", "redetected")
-
-
-def _gpu_rows(tracks):
-    return [(t["id"], t["x"], t["y"], t["width"], t["height"], t["pred_x"], t["pred_y"], t["pred_w"],
-             t["pred_h"], t["age"], t["total_visible"], t["npoints"]) for t in tracks]
-
-
-def run_pair(gpu, W, H, N, F, seed, drop=0.0):
-    from opencv_amd import klt, tbd
-
-    frames, gt = klt.synth_render(seed, W, H, N, 0, F, ctx=gpu)
-    ofr, ogt = L.O.synth(seed, W, H, N, 0, F)  # the oracle's own rendering of the sequence
-    assert np.array_equal(frames.cpu().numpy(), ofr) and np.array_equal(gt.numpy(), ogt)
-    rng = np.random.default_rng(seed)
-    keep = [rng.random(N) >= drop for _ in range(F)]
-    dets = []
-    for f in range(F):
-        d = tbd.detections_from_gt(ogt[f])
-        dets.append(np.ascontiguousarray(d[keep[f][d["id"]]]))
-
-    cfg = tbd.default_config(W, H)  # reference bounds (0, 1280, 0, 720), the bench's options
-    loop = tbd.TbdLoop(cfg, ctx=gpu)
-    ora = L.KltTbdLoop(W, H, nthreads=min(16, os.cpu_count() or 1))
-    gms = []
-    stats = {"pred_err": 0.0, "preds": 0, "refreshed": 0, "lost": 0}
-    for f in range(F):
-        m = loop.step(frames[f], f, dets[f], next_frame=frames[f + 1] if f + 1 < F else None)
-        om = ora.step(ofr[f], f, L.detections(ogt[f], f, keep[f]))
-        gm = {k: getattr(m, k) for k in METRIC_KEYS}
-        gms.append(gm)
-        assert gm == om, f"frame {f}: metrics {gm} vs oracle {om}"
-        gp, op = loop.predictions(), ora.preds
-        assert gp.keys() == op.keys(), f"frame {f}: predicted tracks differ"
-        for k, (cx, cy) in gp.items():
-            e = max(abs(cx - op[k][0]), abs(cy - op[k][1]))
-            assert e <= 1e-4, f"frame {f} track {k}: centre {cx, cy} vs {op[k]}"
-            stats["pred_err"] = max(stats["pred_err"], e)
-        stats["preds"] += len(gp)
-        stats["refreshed"] += om["redetected"]
-        stats["lost"] += om["lk_points"] - om["klt_points"]
-        assert _gpu_rows(loop.tracks()) == ora.track_rows(), f"frame {f}: tracks differ"
-    # the native frame loop (tbdk_tbd_run) over the same frames: the same frames out
-    batch = tbd.TbdLoop(cfg, ctx=gpu)
-    ms = batch.run([frames[f] for f in range(F)], 0, dets)
-    assert [{k: getattr(m, k) for k in METRIC_KEYS} for m in ms] == gms
-    assert _gpu_rows(batch.tracks()) == ora.track_rows()
-    torch.cuda.synchronize()
-    return stats
 
 
 @pytest.mark.parametrize("seed,drop", [(SEED, 0.0), (SEED + 1, 0.1)])

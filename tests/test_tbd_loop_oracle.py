@@ -7,10 +7,12 @@ import os
 import sys
 
 import numpy as np
+import pytest
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 sys.path.insert(0, os.path.join(ROOT, "oracle"))
 import tbd_loop_oracle as L  # noqa: E402
+import _loop_pair as LP  # noqa: E402
 
 
 def test_loop_oracle_tracks_synthetic_objects():
@@ -73,3 +75,28 @@ def test_bench_cpu_baseline_leg_runs_on_cpu():
         for f in range(6):
             assert a.step(fr[f], f, L.detections(gt[f], f)) == b.step(fr[f], f, L.detections(gt[f], f))
             assert a.track_rows() == b.track_rows()
+
+
+@pytest.mark.parametrize("cid", LP.CASE_IDS)
+def test_config_matrix_cases_exercise_the_oracle(cid):
+    """The preconditions of tests/test_gpu_tbd_configs.py, without a GPU: on every
+    case's inputs the oracle alone predicts, refreshes and tracks points, and
+    the case-specific conditions hold (tests/_loop_pair.py,
+    check_oracle_activity: the fit gate holds predictions back, the eigenvalue
+    gate drops points, the slot pool runs out, ...)."""
+    LP.check_oracle_activity(LP.BY_ID[cid])
+
+
+def test_config_matrix_oracle_kwargs_cover_the_config():
+    """Every loop-config field but the frame size and use_klt reaches the
+    oracle under its own name for it; an unknown field is an error."""
+    sys.path.insert(0, ROOT)
+    from opencv_amd import _lib
+
+    fields = [f for f, _ in _lib.TbdConfig._fields_ if f not in ("width", "height", "use_klt")]
+    kw = LP.oracle_kwargs({f: 1 for f in fields})
+    assert kw.pop("bounds") == (1, 1, 1, 1)
+    L.KltTbdLoop(64, 64, **kw)  # every name is one the oracle takes
+    assert len(kw) == len(fields) - 4
+    with pytest.raises(KeyError):
+        LP.oracle_kwargs({"use_klt": 0})
