@@ -249,6 +249,15 @@ int tbdk_ctx_set_option(tbdk_ctx* ctx, const char* name, int64_t value);
  *       corners (see tbdk_box_propagate_ransac); a track without consensus
  *       gets no KLT prediction in that frame.  The tracked sets themselves
  *       are unchanged (outlier corners are kept).
+ *   "tbd_fb_check" (0..1048576, default 0; taken by tbdk_tbd_create): 0: off;
+ *       N > 0: every PyrLK launch of the TBD loop is followed by the backward
+ *       pass of the forward-backward check (see tbdk_lk_sparse_fb) with
+ *       back_threshold = N / 1024 px (1024: the reference samples' 1.0 px).  A
+ *       corner that fails it leaves its track's set before the fit, so the fit
+ *       (least squares or tbd_fit_ransac), min_points and min_fit_points see
+ *       the kept pairs only.  tbdk_frame_metrics: lk_points counts the points
+ *       entering the forward pass, klt_points the pairs kept after the check,
+ *       lk_iters the forward pass's iterations.
  *   "tbd_async_la" (0/1, default 0; taken by tbdk_tbd_create): the TBD loop's
  *       look-ahead PyrLK launches are issued by a worker thread of the loop
  *       (one more host thread per loop, spinning between frames; results equal;
@@ -398,6 +407,37 @@ int tbdk_pyr_down_u8(tbdk_ctx* ctx, const uint8_t* src, int width, int height, i
 int tbdk_lk_sparse(tbdk_ctx* ctx, const tbdk_pyr* prev, const tbdk_pyr* next,
                    const float* prev_pts, float* next_pts, uint8_t* status, float* err,
                    int32_t* iters, int n, const tbdk_lk_params* params, void* stream);
+
+/* tbdk_lk_sparse with the forward-backward check of the reference's KLT tracker
+ * samples (samples/python/lk_track.py:57-60, checkedTrace in
+ * samples/python/lk_homography.py:42-47): the points tracked prev -> next are
+ * tracked back next -> prev by a second launch on the same stream (no host
+ * synchronisation in between), and a point keeps status 1 iff the forward
+ * status is 1, the backward status is 1 and
+ *   d = max(|p0.x - p0r.x|, |p0.y - p0r.y|) < back_threshold     (float32)
+ * with p0 its prev_pts entry and p0r the point tracked back.  (The samples
+ * ignore both statuses; a lost point's coordinates are leftovers of a coarser
+ * level, so here both gate the result.)
+ *   The backward pass has the forward pass's window, max_level, criteria and
+ * min_eig_threshold, flags 0 (it starts at the forward result whether or not
+ * the forward pass took an initial flow, and computes no error), and skips the
+ * points whose forward status is 0.  params->impl chooses the forward kernel
+ * only.
+ *   next_pts / err / iters : the forward pass's, bit for bit what tbdk_lk_sparse
+ *                            gives, also for rejected points
+ *   status                 : as above
+ *   back_pts               : n x float2 or NULL: p0r where the forward status
+ *                            is 1, the prev_pts entry elsewhere
+ *   fb_err                 : n x f32 or NULL: d where both statuses are 1,
+ *                            +inf elsewhere
+ * back_threshold must be > 0 (+inf: only the statuses gate; NaN or <= 0 is
+ * TBDK_EINVAL).  8-bit one-channel pyramids only (padded, with or without
+ * derivative planes, or with a borrowed level 0): multi-channel, 16F and 32F
+ * pyramids are TBDK_EINVAL.  n == 0 is a no-op.  Timed as "lk_sparse" and
+ * "lk_sparse_back". */
+int tbdk_lk_sparse_fb(tbdk_ctx* ctx, const tbdk_pyr* prev, const tbdk_pyr* next, const float* prev_pts,
+                      float* next_pts, uint8_t* status, float* err, int32_t* iters, float* back_pts,
+                      float* fb_err, int n, const tbdk_lk_params* params, float back_threshold, void* stream);
 
 /* Replaces cv::cuda::DensePyrLKOpticalFlow::calc(I0, I1, flow)
  * (cudaoptflow/include/opencv2/cudaoptflow.hpp:182-208, impl cudaoptflow/src/pyrlk.cpp:238-299)

@@ -249,6 +249,48 @@ public:
               "tbdk_lk_sparse");
     }
 
+    // calc with the forward-backward check of the reference's KLT tracker samples
+    // (checkedTrace, samples/python/lk_homography.py:42-47; tbdk_lk_sparse_fb):
+    // the tracked points are tracked back nextImg -> prevImg, and status stays 1
+    // only where both passes have status 1 and max(|dx|, |dy|) between prevPts
+    // and the point tracked back is below backThreshold.  nextPts and err are
+    // calc's; fbErr (n floats, may be null) gets that distance, +inf where
+    // either pass lost the point.  8-bit one-channel images.
+    void calcChecked(const GpuImage& prevImg, const GpuImage& nextImg, const float* prevPts, float* nextPts,
+                     uint8_t* status, int n, float backThreshold = 1.0f, float* err = nullptr,
+                     float* fbErr = nullptr, void* stream = nullptr)
+    {
+        if (n == 0) return;
+        for (int i = 0; i < 2; ++i) {
+            const GpuImage& im = i == 0 ? prevImg : nextImg;
+            if (!pyr_[i] || pyr_[i]->get().lv[0].width != im.width || pyr_[i]->get().lv[0].height != im.height ||
+                pyr_[i]->depth() != TBDK_DEPTH_8U || pyr_[i]->channels() != 1)
+                pyr_[i].reset(new Pyramid(*ctx_, im.width, im.height, max_level_, win_));
+            pyr_[i]->build(im, stream);
+        }
+        calcChecked(*pyr_[0], *pyr_[1], prevPts, nextPts, status, n, backThreshold, err, fbErr, stream);
+    }
+
+    // the same on prebuilt pyramids; backPts (n float2, may be null): the points tracked back
+    void calcChecked(const Pyramid& prev, const Pyramid& next, const float* prevPts, float* nextPts, uint8_t* status,
+                     int n, float backThreshold = 1.0f, float* err = nullptr, float* fbErr = nullptr,
+                     void* stream = nullptr, float* backPts = nullptr, int32_t* iters = nullptr)
+    {
+        tbdk_lk_params p;
+        p.win_w = win_.width;
+        p.win_h = win_.height;
+        p.max_level = max_level_;
+        p.max_count = iters_;
+        p.epsilon = eps_;
+        p.flags = (use_initial_flow_ ? TBDK_OPTFLOW_USE_INITIAL_FLOW : 0) |
+                  (min_eig_flag_ ? TBDK_OPTFLOW_LK_GET_MIN_EIGENVALS : 0);
+        p.min_eig_threshold = min_eig_;
+        p.impl = 0;
+        check(tbdk_lk_sparse_fb(ctx_->get(), &prev.get(), &next.get(), prevPts, nextPts, status, err, iters, backPts,
+                                fbErr, n, &p, backThreshold, stream),
+              "tbdk_lk_sparse_fb");
+    }
+
 private:
     SparsePyrLKOpticalFlow(Context& ctx, Size win, int max_level, int iters, bool uif)
         : ctx_(&ctx), win_(win), max_level_(max_level), iters_(iters), use_initial_flow_(uif)

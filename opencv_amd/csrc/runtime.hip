@@ -239,6 +239,11 @@ int tbdk_ctx_set_option(tbdk_ctx* ctx, const char* name, int64_t value)
         ctx->opt_tbd_fit_ransac = (int)value;
         return TBDK_OK;
     }
+    if (std::strcmp(name, "tbd_fb_check") == 0) {
+        if (value < 0 || value > 1048576) return TBDK_EINVAL;
+        ctx->opt_tbd_fb_check = (int)value;
+        return TBDK_OK;
+    }
     if (std::strcmp(name, "tbd_fit_gate") == 0) {
         ctx->opt_tbd_fit_gate = value != 0;
         return TBDK_OK;
@@ -639,15 +644,32 @@ int tbdk_lk_sparse(tbdk_ctx* ctx, const tbdk_pyr* prev, const tbdk_pyr* next, co
     return tbdk::lk_internal(ctx, prev, next, prev_pts, next_pts, status, err, iters, n, p, nullptr, 0, stream);
 }
 
+int tbdk_lk_sparse_fb(tbdk_ctx* ctx, const tbdk_pyr* prev, const tbdk_pyr* next, const float* prev_pts,
+                      float* next_pts, uint8_t* status, float* err, int32_t* iters, float* back_pts, float* fb_err,
+                      int n, const tbdk_lk_params* p, float back_threshold, void* stream)
+{
+    if (!ctx || !prev || !next || !p || n < 0 || !(back_threshold > 0.f)) return TBDK_EINVAL;
+    // u8 one-channel frames only (checked before the forward launch: nothing runs on a refusal)
+    if (prev->depth != TBDK_DEPTH_8U || next->depth != TBDK_DEPTH_8U || prev->cn > 1 || next->cn > 1)
+        return TBDK_EINVAL;
+    const int r = tbdk::lk_internal(ctx, prev, next, prev_pts, next_pts, status, err, iters, n, p, nullptr, 0, stream);
+    if (r != TBDK_OK || n == 0) return r;
+    const tbdk::LkBack back{back_pts, fb_err, back_threshold};
+    return tbdk::lk_internal(ctx, next, prev, prev_pts, next_pts, status, nullptr, nullptr, n, p, nullptr, 0, stream,
+                             nullptr, nullptr, nullptr, &back);
+}
+
 }  // extern "C"
 
 int tbdk::lk_internal(tbdk_ctx* ctx, const tbdk_pyr* prev, const tbdk_pyr* next, const float* prev_pts,
                       float* next_pts, uint8_t* status, float* err, int32_t* iters, int n, const tbdk_lk_params* p,
                       const int32_t* seg_counts, int seg_stride, void* stream, const int32_t* seg_list,
-                      const LkDense* dense, const int32_t* seg_list_host)
+                      const LkDense* dense, const int32_t* seg_list_host, const LkBack* back)
 {
     if (!ctx || !prev || !next || !p || n < 0) return TBDK_EINVAL;
     if (n == 0) return TBDK_OK;
+    if (back && (dense || !(back->thr > 0.f) || prev->depth != TBDK_DEPTH_8U || prev->cn > 1 || next->cn > 1))
+        return TBDK_EINVAL;
     if (dense ? !dense->flow : (!prev_pts || !next_pts || !status)) return TBDK_EINVAL;
     if (p->win_w <= 2 || p->win_h <= 2 || p->win_w > 63 || p->win_h > 63 || p->max_level < 0) return TBDK_EINVAL;
     if (prev->nlevels <= 0 || next->nlevels <= 0) return TBDK_EINVAL;
@@ -675,8 +697,9 @@ int tbdk::lk_internal(tbdk_ctx* ctx, const tbdk_pyr* prev, const tbdk_pyr* next,
         if ((I.pad < pad_needed && !bI) || (J.pad < pad_needed && !bJ)) return TBDK_EINVAL;
         const tbdk_level& D = prev->dv[l];
         const int impl_eff = p->impl ? p->impl : ctx->opt_lk_impl;
-        if ((bI || bJ) && (dense || cn > 1 || f16 || D.data || !lk_multi_supported(p->win_w, p->win_h) ||
-                           (impl_eff != 0 && impl_eff != 3)))
+        if ((bI || bJ) && !lk_multi_supported(p->win_w, p->win_h)) return TBDK_EINVAL;
+        // (the backward pass runs that kernel whatever impl says, and reads no planes)
+        if ((bI || bJ) && !back && (dense || cn > 1 || f16 || D.data || (impl_eff != 0 && impl_eff != 3)))
             return TBDK_EINVAL;
         a.lv[l] = LkLevel{I.data, J.data, D.data, I.width, I.height, I.pitch, J.pitch, I.pad, J.pad, D.pitch, D.pad};
     }
@@ -686,7 +709,7 @@ int tbdk::lk_internal(tbdk_ctx* ctx, const tbdk_pyr* prev, const tbdk_pyr* next,
     a.max_count = p->max_count < 0 ? 0 : (p->max_count > 100 ? 100 : p->max_count);
     double eps = p->epsilon < 0. ? 0. : (p->epsilon > 10. ? 10. : p->epsilon);
     a.eps2 = eps * eps;
-    a.flags = p->flags;
+    a.flags = back ? 0 : p->flags;
     a.min_eig = p->min_eig_threshold;
     a.prev_pts = prev_pts;
     a.next_pts = next_pts;
@@ -755,6 +778,18 @@ int tbdk::lk_internal(tbdk_ctx* ctx, const tbdk_pyr* prev, const tbdk_pyr* next,
         if (p->impl != 0 || !have_d || !lk_f16_supported(p->win_w, p->win_h)) return TBDK_EINVAL;
         int rec = timing_begin(ctx, "lk_sparse", s);
         hipError_t e = launch_lk_f16(a, f32, s);
+        timing_end(ctx, rec, s);
+        return map_err(e);
+    }
+    if (back) {
+        // the backward pass of the forward-backward check: the caller passed the
+        // pyramids swapped, the forward pass's start as prev_pts and its results
+        // as next_pts / status.  Scharr values on the fly (the pyramid the forward
+        // pass tracked into need not carry planes); the generic kernel for the
+        // windows the several-points-per-wave kernel has no instance of
+        int rec = timing_begin(ctx, "lk_sparse_back", s);
+        hipError_t e = lk_multi_supported(p->win_w, p->win_h) ? launch_lk_multi_back(a, *back, s)
+                                                                : launch_lk_sparse_back(a, *back, s);
         timing_end(ctx, rec, s);
         return map_err(e);
     }

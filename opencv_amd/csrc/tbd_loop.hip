@@ -449,6 +449,7 @@ struct tbdk_tbd {
     // system scope; d_fitcnt counts the finished waves
     bool fit_flag = false;
     int fit_ransac = 0;  // ctx option tbd_fit_ransac at create: RANSAC rounds of the fit, 0 = least squares
+    int fb_check = 0;    // ctx option tbd_fb_check at create: forward-backward threshold in 1/1024 px, 0 = off
     int32_t* h_flag = nullptr;
     int32_t* d_flag = nullptr;
     unsigned* d_fitcnt = nullptr;
@@ -506,6 +507,24 @@ inline int run_or_post(tbdk_tbd* t, std::function<int()> f)
     if (!t->worker) return f();
     t->worker->post(std::move(f));
     return TBDK_OK;
+}
+
+// Every PyrLK launch of the loop: n launch indices over the segment list
+// (d_list on the device, h_list its host copy), pyramid A -> B on stream s.
+// With ctx option tbd_fb_check the backward pass (B -> A over the same list)
+// follows on the same stream, before any event the caller records for the
+// launch: the fit then compacts on the checked status.
+int loop_lk(tbdk_tbd* t, const tbdk_pyr* A, const tbdk_pyr* B, int n, const tbdk_lk_params& lp, hipStream_t s,
+            const int32_t* d_list, const int32_t* h_list)
+{
+    const float* pts = reinterpret_cast<const float*>(t->slot_pts);
+    float* nxt = reinterpret_cast<float*>(t->slot_next);
+    const int r = lk_internal(t->ctx, A, B, pts, nxt, t->slot_status, nullptr, t->slot_iters, n, &lp, t->slot_counts,
+                              kSlotPts, s, d_list, nullptr, h_list);
+    if (r != TBDK_OK || t->fb_check <= 0) return r;
+    const LkBack back{nullptr, nullptr, (float)t->fb_check * (1.f / 1024.f)};
+    return lk_internal(t->ctx, B, A, pts, nxt, t->slot_status, nullptr, nullptr, n, &lp, t->slot_counts, kSlotPts, s,
+                       d_list, nullptr, h_list, &back);
 }
 
 // a frame's pyramid into P: borrowed level 0 inside tbdk_tbd_run (levels 1..
@@ -710,6 +729,7 @@ int tbdk_tbd_create(tbdk_ctx* ctx, const tbdk_tbd_config* cfg, tbdk_tbd** out)
     sm(reinterpret_cast<void**>(&t->d_etab), t->h_etab[0], kEarlySets * sizeof(GfttRoi) * S);
     t->fit_flag = t->zc && ctx->opt_tbd_fit_flag != 0;
     t->fit_ransac = ctx->opt_tbd_fit_ransac;
+    t->fb_check = ctx->opt_tbd_fb_check;
     if (t->fit_flag) {
         hm(reinterpret_cast<void**>(&t->h_flag), 64);
         sm(reinterpret_cast<void**>(&t->d_flag), t->h_flag, 64);
@@ -1149,9 +1169,7 @@ int step_impl(tbdk_tbd* t, const uint8_t* frame, int pitch, int frame_id, const 
             if (e == hipSuccess && !t->zc)
                 e = hipMemcpyAsync(t->d_la, t->h_la, sizeof(int32_t) * n, hipMemcpyHostToDevice, ls);
             if (e != hipSuccess) return map_status(e);
-            const int r = lk_internal(t->ctx, pa, pb, reinterpret_cast<const float*>(t->slot_pts),
-                                      reinterpret_cast<float*>(t->slot_next), t->slot_status, nullptr, t->slot_iters,
-                                      n * kSlotPts, &lp, t->slot_counts, kSlotPts, ls, t->d_la, nullptr, t->h_la);
+            const int r = loop_lk(t, pa, pb, n * kSlotPts, lp, ls, t->d_la, t->h_la);
             if (r != TBDK_OK) return r;
             return map_status(hipEventRecord(t->la_done, ls));
         });
@@ -1187,9 +1205,7 @@ int step_impl(tbdk_tbd* t, const uint8_t* frame, int pitch, int frame_id, const 
         // and one launch of nA + nB sets replaces two back-to-back ones
         merged = nA > 0 && nB > 0 && (!t->post_wait || hipEventQuery(t->post_wait) == hipSuccess);
         if (nA > 0 && !merged) {
-            rc = lk_internal(t->ctx, &Pprev, &P, reinterpret_cast<const float*>(t->slot_pts),
-                             reinterpret_cast<float*>(t->slot_next), t->slot_status, nullptr, t->slot_iters,
-                             nA * kSlotPts, &lp, t->slot_counts, kSlotPts, s, t->d_lists, nullptr, t->h_lists);
+            rc = loop_lk(t, &Pprev, &P, nA * kSlotPts, lp, s, t->d_lists, t->h_lists);
             if (rc != TBDK_OK) return rc;
         }
     }
@@ -1236,10 +1252,7 @@ int step_impl(tbdk_tbd* t, const uint8_t* frame, int pitch, int frame_id, const 
     if (run_klt) {
         if (nB > 0) {
             const int first = merged ? 0 : nA, nsets = merged ? nA + nB : nB;
-            rc = lk_internal(t->ctx, &Pprev, &P, reinterpret_cast<const float*>(t->slot_pts),
-                             reinterpret_cast<float*>(t->slot_next), t->slot_status, nullptr, t->slot_iters,
-                             nsets * kSlotPts, &lp, t->slot_counts, kSlotPts, s, t->d_lists + first, nullptr,
-                             t->h_lists + first);
+            rc = loop_lk(t, &Pprev, &P, nsets * kSlotPts, lp, s, t->d_lists + first, t->h_lists + first);
             if (rc != TBDK_OK) return rc;
         }
         if (la_defer > 0) {
@@ -1427,10 +1440,7 @@ int step_impl(tbdk_tbd* t, const uint8_t* frame, int pitch, int frame_id, const 
                     if (e2 == hipSuccess && !t->zc)
                         e2 = hipMemcpyAsync(t->d_spec, t->h_spec, sizeof(int32_t) * ns, hipMemcpyHostToDevice, ls);
                     if (e2 != hipSuccess) return map_status(e2);
-                    const int r = lk_internal(t->ctx, pa, pb, reinterpret_cast<const float*>(t->slot_pts),
-                                              reinterpret_cast<float*>(t->slot_next), t->slot_status, nullptr,
-                                              t->slot_iters, ns * kSlotPts, &lp, t->slot_counts, kSlotPts, ls,
-                                              t->d_spec, nullptr, t->h_spec);
+                    const int r = loop_lk(t, pa, pb, ns * kSlotPts, lp, ls, t->d_spec, t->h_spec);
                     if (r != TBDK_OK) return r;
                     return map_status(hipEventRecord(t->la_done, ls));
                 });
@@ -1467,9 +1477,7 @@ int step_impl(tbdk_tbd* t, const uint8_t* frame, int pitch, int frame_id, const 
             if (e == hipSuccess && !t->zc)
                 e = hipMemcpyAsync(t->d_ers, t->h_ers, sizeof(int32_t) * ne, hipMemcpyHostToDevice, ls);
             if (e != hipSuccess) return map_status(e);
-            rc = lk_internal(t->ctx, &P, &Pnext, reinterpret_cast<const float*>(t->slot_pts),
-                             reinterpret_cast<float*>(t->slot_next), t->slot_status, nullptr, t->slot_iters,
-                             ne * kSlotPts, &lp, t->slot_counts, kSlotPts, ls, t->d_ers, nullptr, t->h_ers);
+            rc = loop_lk(t, &P, &Pnext, ne * kSlotPts, lp, ls, t->d_ers, t->h_ers);
             if (rc != TBDK_OK) return rc;
             e = hipEventRecord(t->la_done, ls);
             if (e != hipSuccess) return map_status(e);

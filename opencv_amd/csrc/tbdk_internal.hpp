@@ -109,6 +109,7 @@ struct tbdk_ctx {
     int opt_tbd_borrow_l0 = 0;   // tbdk_ctx_set_option("tbd_borrow_l0"): tbdk_tbd_run's pyramids take the frame as level 0 (A/B)
     int opt_tbd_fit_gate = 1;    // tbdk_ctx_set_option("tbd_fit_gate"): the host launches the fit once the look-ahead PyrLK is done
     int opt_tbd_fit_ransac = 0;  // tbdk_ctx_set_option("tbd_fit_ransac"): RANSAC rounds of the loop's fit, 0 = least squares (read by tbdk_tbd_create)
+    int opt_tbd_fb_check = 0;    // tbdk_ctx_set_option("tbd_fb_check"): the loop's forward-backward check, threshold in 1/1024 px, 0 = off (read by tbdk_tbd_create)
     int opt_tbd_async_la = 0;    // tbdk_ctx_set_option("tbd_async_la"): look-ahead launches by a worker thread (read by tbdk_tbd_create)
     std::string timing_only;  // ",name,name," filter of tbdk_timing_select ("" = all)
     int timing_every = 1;     // tbdk_ctx_set_option("timing_every"): events on every Nth selected launch
@@ -195,6 +196,18 @@ struct LkLevel {
     int cpitch;
 };
 
+// backward pass of the forward-backward check (tbdk_lk_sparse_fb, the TBD
+// loop's tbd_fb_check; lk_multi_back_kernel, lk_sparse_back_kernel): lk_internal
+// is then called with the two pyramids swapped, prev_pts the forward pass's
+// start, next_pts its result (read only) and status its status, cleared where
+// the point tracked back is lost or lies thr or more from prev_pts.  A second
+// kernel argument: LkArgs, and with it the forward kernels' code, stays as it is
+struct LkBack {
+    float* back_pts;  // optional: the point tracked back (prev_pts where the forward status is 0)
+    float* fb_err;    // optional: max(|dx|, |dy|) to prev_pts (+inf where either status is 0)
+    float thr;        // > 0 (+inf: only the statuses gate)
+};
+
 constexpr int kSegInline = 256;  // segment list entries LkArgs can carry itself
 
 struct LkArgs {
@@ -263,7 +276,8 @@ struct LkDense {
 int lk_internal(tbdk_ctx* ctx, const tbdk_pyr* prev, const tbdk_pyr* next, const float* prev_pts, float* next_pts,
                 uint8_t* status, float* err, int32_t* iters, int n, const tbdk_lk_params* p,
                 const int32_t* seg_counts, int seg_stride, void* stream, const int32_t* seg_list = nullptr,
-                const LkDense* dense = nullptr, const int32_t* seg_list_host = nullptr);
+                const LkDense* dense = nullptr, const int32_t* seg_list_host = nullptr,
+                const LkBack* back = nullptr);
 int map_status(hipError_t e);
 // multi-channel u8 pyramids and PyrLK (klt_cn.hip)
 hipError_t launch_pyr_cn(const uint8_t* img, int pitch, const tbdk_pyr& pyr, hipStream_t s);
@@ -283,6 +297,10 @@ hipError_t launch_lk_strip(const LkArgs& a, hipStream_t s);
 bool lk_multi_supported(int win_w, int win_h);
 // fly: Scharr derivatives computed in the kernel (no derivative planes read)
 hipError_t launch_lk_multi(const LkArgs& a, bool fly, hipStream_t s);
+// backward pass of the forward-backward check (Scharr on the fly): a.lv holds
+// the swapped pyramids, a.next_pts / a.status the forward results
+hipError_t launch_lk_multi_back(const LkArgs& a, const LkBack& b, hipStream_t s);
+hipError_t launch_lk_sparse_back(const LkArgs& a, const LkBack& b, hipStream_t s);
 // dense mode of the several-points-per-wave kernel (klt_dense.hip: case images in a.lv[].C)
 hipError_t launch_lk_multi_dense(const LkArgs& a, hipStream_t s);
 // the fp16 pixel path (klt_f16.hip)

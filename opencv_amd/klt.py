@@ -462,6 +462,14 @@ class LkResult:
     iters: torch.Tensor | None
 
 
+@dataclass
+class LkCheckedResult(LkResult):
+    """calc_checked: the forward pass's LkResult with the checked status, plus the
+    points tracked back and their distance to prevPts"""
+    back_pts: torch.Tensor
+    fb_err: torch.Tensor
+
+
 class SparsePyrLKOpticalFlow:
     """cv::cuda::SparsePyrLKOpticalFlow with the CPU calcOpticalFlowPyrLK numerics.
 
@@ -556,6 +564,43 @@ class SparsePyrLKOpticalFlow:
             C.c_void_p(iters.data_ptr()) if iters is not None else None, n, C.byref(prm), _stream_ptr(stream)),
             "tbdk_lk_sparse")
         return LkResult(out, status, err, iters)
+
+    def calc_checked(self, prevImg, nextImg, prevPts: torch.Tensor, nextPts: torch.Tensor | None = None,
+                     back_threshold: float = 1.0, want_err: bool = True, want_iters: bool = False,
+                     stream=None) -> LkCheckedResult:
+        """calc with the forward-backward check (tbdk_lk_sparse_fb; the reference
+        samples' checkedTrace): the tracked points are tracked back nextImg ->
+        prevImg, and status stays 1 only where both passes have status 1 and
+        max(|dx|, |dy|) between prevPts and the point tracked back is below
+        back_threshold.  next_pts / err / iters are calc's.  back_pts: the points
+        tracked back (prevPts where the forward pass lost the point); fb_err: that
+        distance (+inf where either pass lost the point).  8-bit one-channel
+        frames only."""
+        if prevPts.dtype != torch.float32 or not prevPts.is_cuda:
+            raise _lib.TbdkError("prevPts must be a float32 device tensor of shape (N, 2)")
+        pts = prevPts.reshape(-1, 2).contiguous()
+        n = pts.shape[0]
+        dev = pts.device
+        P, N = self._as_pyr(prevImg), self._as_pyr(nextImg)
+        if self.use_initial_flow:
+            if nextPts is None or nextPts.numel() != 2 * n:
+                raise _lib.TbdkError("useInitialFlow requires nextPts of the same size as prevPts")
+            out = nextPts.reshape(-1, 2).to(torch.float32).contiguous().clone()
+        else:
+            out = torch.empty((n, 2), dtype=torch.float32, device=dev)
+        status = torch.empty((n,), dtype=torch.uint8, device=dev)
+        err = torch.empty((n,), dtype=torch.float32, device=dev) if want_err else None
+        iters = torch.empty((n,), dtype=torch.int32, device=dev) if want_iters else None
+        back = torch.empty((n, 2), dtype=torch.float32, device=dev)
+        fb_err = torch.empty((n,), dtype=torch.float32, device=dev)
+        prm = self.params()
+        _lib.check(self.ctx.lib.tbdk_lk_sparse_fb(
+            self.ctx.handle, C.byref(P.pyr), C.byref(N.pyr), C.c_void_p(pts.data_ptr()), C.c_void_p(out.data_ptr()),
+            C.c_void_p(status.data_ptr()), C.c_void_p(err.data_ptr()) if err is not None else None,
+            C.c_void_p(iters.data_ptr()) if iters is not None else None, C.c_void_p(back.data_ptr()),
+            C.c_void_p(fb_err.data_ptr()), n, C.byref(prm), C.c_float(back_threshold), _stream_ptr(stream)),
+            "tbdk_lk_sparse_fb")
+        return LkCheckedResult(out, status, err, iters, back, fb_err)
 
 
 class DensePyrLKOpticalFlow(SparsePyrLKOpticalFlow):
