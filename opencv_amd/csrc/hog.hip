@@ -204,21 +204,16 @@ __device__ __forceinline__ float hog_fast_atan(float y, float x, bool vec)
     const float p5 = 0.1555786518463281f * (float)(180 / M_PI);
     const float p7 = -0.04432655554792128f * (float)(180 / M_PI);
     const float ax = fabsf(x), ay = fabsf(y);
+    // v_atan_f32::compute (mathfuncs_core.simd.hpp:92-103), FMA form.  The scalar
+    // atan_f32 (:50-71) of the same AVX2 unit is FMA-contracted by gcc: the same
+    // chain, and "90 - poly * c" as one fused multiply-subtract, the only difference
+    const float c = fminf(ax, ay) / (fmaxf(ax, ay) + (float)DBL_EPSILON);
+    const float cc = c * c;
+    const float poly = fmaf(fmaf(fmaf(cc, p7, p5), cc, p3), cc, p1);
     float a;
-    if (vec) {  // v_atan_f32::compute (mathfuncs_core.simd.hpp:92-103), FMA form
-        const float c = fminf(ax, ay) / (fmaxf(ax, ay) + (float)DBL_EPSILON);
-        const float cc = c * c;
-        a = fmaf(fmaf(fmaf(cc, p7, p5), cc, p3), cc, p1) * c;
-        if (!(ax >= ay)) a = 90.f - a;
-    } else {  // atan_f32 (:50-71)
-        if (ax >= ay) {
-            const float c = ay / (ax + (float)DBL_EPSILON), c2 = c * c;
-            a = (((p7 * c2 + p5) * c2 + p3) * c2 + p1) * c;
-        } else {
-            const float c = ax / (ay + (float)DBL_EPSILON), c2 = c * c;
-            a = 90.f - (((p7 * c2 + p5) * c2 + p3) * c2 + p1) * c;
-        }
-    }
+    if (ax >= ay) a = poly * c;
+    else if (vec) a = 90.f - poly * c;
+    else a = fmaf(-c, poly, 90.f);
     if (x < 0) a = 180.f - a;
     if (y < 0) a = 360.f - a;
     return a * (float)(M_PI / 180);
@@ -257,7 +252,7 @@ __global__ __launch_bounds__(256) void hog_grad_kernel(HogGradArgs a)
         dy = k == 0 ? ddy[0] : k == 1 ? ddy[1] : ddy[2];
     }
     const int vec = a.w - (x & ~1023) >= a.vec_min_len;  // length of x's 1024-chunk >= 16
-    const float m = vec ? sqrtf(fmaf(dx, dx, dy * dy)) : sqrtf(dx * dx + dy * dy);
+    const float m = sqrtf(fmaf(dx, dx, dy * dy));  // both forms: the scalar one is contracted the same way
     float ang = hog_fast_atan(dy, dx, vec) * a.angle_scale - 0.5f;
     int hidx = (int)floorf(ang);
     ang -= hidx;

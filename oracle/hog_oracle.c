@@ -15,7 +15,8 @@
  *                                  the scalar tail's different tie rules, bin split)
  *   cartToPolar -> magnitude32f / fastAtan32f  core/src/mathfuncs_core.simd.hpp:76-225,
  *                                  the AVX2 dispatch (8 lanes, FMA) the reference selects at
- *                                  run time on an x86-64 host; scalar for rows < 16 pixels
+ *                                  run time on an x86-64 host; for rows < 16 pixels that unit's
+ *                                  scalar code, which gcc contracts to FMA as well
  *   HOGCache::init / getBlock      hog.cpp:619-1117 (Gaussian block weights, pixData
  *                                  tables in count1/count2/count4 order, SSE2 weights)
  *   normalizeBlockHistogram        hog.cpp:1119-1248 (4-lane partial sums, L2-Hys)
@@ -24,8 +25,12 @@
  *   groupRectangles                hog.cpp:3783-3861 with partition() and SimilarRects
  *                                  (core/include/opencv2/core/operations.hpp,
  *                                  objdetect.hpp) and clipObjects (cascadedetect.cpp:1683)
- * Parity against the reference binaries is unpinned: the reference's HOG tests
- * read images from opencv_extra, which is not vendored.
+ * Pinned to the reference binaries' default runtime dispatch (AVX2 on) by
+ * tests/golden/reference_hog.npz: computeGradient, detect() scores and
+ * detectMultiScale() rects bit for bit (tests/test_reference_pins.py).  With AVX2
+ * disabled the reference's cartToPolar rounds differently (about 92 % of the
+ * gradient words equal; tools/record_reference_cases.md), which this file does
+ * not model.
  */
 #include <float.h>
 #include <math.h>
@@ -128,32 +133,23 @@ static const float kAtanP3 = -0.3258083974640975f * (float)(180 / M_PI);
 static const float kAtanP5 = 0.1555786518463281f * (float)(180 / M_PI);
 static const float kAtanP7 = -0.04432655554792128f * (float)(180 / M_PI);
 
-/* fastAtan32f element: vector form (v_atan_f32::compute, FMA) or scalar atan_f32 */
+/* fastAtan32f element: vector form (v_atan_f32::compute, FMA) or the scalar atan_f32 of
+ * the same AVX2 unit.  That unit is compiled with -mfma, and gcc (fp-contract=fast, its
+ * default) fuses the scalar code too: the polynomial becomes the vector form's FMA chain
+ * and "90 - poly * c" one fused multiply-subtract, which is where the two forms differ
+ * (pinned by tests/golden/reference_hog.npz, the 15-pixel rows). */
 static float fast_atan(float y, float x, int vec)
 {
     const float ax = fabsf(x), ay = fabsf(y);
+    const float c = fminf(ax, ay) / (fmaxf(ax, ay) + (float)DBL_EPSILON);
+    const float cc = c * c;
+    const float poly = fmaf(fmaf(fmaf(cc, kAtanP7, kAtanP5), cc, kAtanP3), cc, kAtanP1);
     float a;
-    if (vec) {
-        const float c = fminf(ax, ay) / (fmaxf(ax, ay) + (float)DBL_EPSILON);
-        const float cc = c * c;
-        a = fmaf(fmaf(fmaf(cc, kAtanP7, kAtanP5), cc, kAtanP3), cc, kAtanP1) * c;
-        if (!(ax >= ay)) a = 90.f - a;
-        if (x < 0) a = 180.f - a;
-        if (y < 0) a = 360.f - a;
-    } else {
-        float c, c2;
-        if (ax >= ay) {
-            c = ay / (ax + (float)DBL_EPSILON);
-            c2 = c * c;
-            a = (((kAtanP7 * c2 + kAtanP5) * c2 + kAtanP3) * c2 + kAtanP1) * c;
-        } else {
-            c = ax / (ay + (float)DBL_EPSILON);
-            c2 = c * c;
-            a = 90.f - (((kAtanP7 * c2 + kAtanP5) * c2 + kAtanP3) * c2 + kAtanP1) * c;
-        }
-        if (x < 0) a = 180.f - a;
-        if (y < 0) a = 360.f - a;
-    }
+    if (ax >= ay) a = poly * c;
+    else if (vec) a = 90.f - poly * c;
+    else a = fmaf(-c, poly, 90.f);
+    if (x < 0) a = 180.f - a;
+    if (y < 0) a = 360.f - a;
     return a * (float)(M_PI / 180);
 }
 
@@ -167,7 +163,8 @@ void orc_hog_gradient(const uint8_t* img, int w, int h, int pitch, int cn, int n
     const float angle_scale = signed_grad ? (float)(nbins / (2.0 * M_PI)) : (float)(nbins / M_PI);
     /* cartToPolar feeds magnitude32f/fastAtan32f 1024-element chunks of the row
      * (core/src/mathfuncs.cpp:285-298, BLOCK_SIZE precomp.hpp:269); a chunk shorter
-     * than 2 x 8 AVX2 lanes runs the scalar forms (mathfuncs_core.simd.hpp:131-138,202-207) */
+     * than 2 x 8 AVX2 lanes runs the scalar forms (mathfuncs_core.simd.hpp:131-138,202-207),
+     * FMA-contracted by the compiler (fast_atan above) */
     const int simd_w = w & ~3;   /* the SSE2 3-channel body */
     for (int y = 0; y < h; y++) {
         const uint8_t* P = img + (size_t)y * pitch;
@@ -198,7 +195,7 @@ void orc_hog_gradient(const uint8_t* img, int w, int h, int pitch, int cn, int n
                 }
             }
             const int chunk = w - (x / 1024) * 1024, vec_mag = (chunk < 1024 ? chunk : 1024) >= 16;
-            const float m = vec_mag ? sqrtf(fmaf(dx, dx, dy * dy)) : sqrtf(dx * dx + dy * dy);
+            const float m = sqrtf(fmaf(dx, dx, dy * dy)); /* the scalar form fuses the same way */
             float ang = fast_atan(dy, dx, vec_mag) * angle_scale - 0.5f;
             int hidx = (int)floorf(ang);
             ang -= hidx;

@@ -5,14 +5,14 @@
  * bench.py's cpu_baseline leg compare the HIP path against.  The product path
  * (opencv_amd/) never links, imports or calls anything under oracle/.
  *
- * Parity status: the reference (OpenCV 3.4.7 fork) cannot be compiled from a
- * few of its own source files (core's headers need the CMake-generated
- * opencv2/opencv_modules.hpp / cvconfig.h), and its golden data for this path
- * lives in the non-vendored opencv_extra.  The restatement below is therefore
- * pinned only by the reference's in-tree known-answer checks
- * (modules/imgproc/test/test_filter.cpp:2298-2304) and by the reference tests'
- * own acceptance criteria, restated in tests/ — i.e. "parity unpinned" against
- * reference-produced vectors.
+ * Parity status: pinned bit for bit to outputs recorded from a build of the
+ * reference (OpenCV 3.4.7 fork), tests/golden/reference_*.npz: pyramid levels,
+ * Scharr planes, calcOpticalFlowPyrLK (ORC_ACCUM_SSE2: points, status, err; 1 to
+ * 4 channels), goodFeaturesToTrack, the corner maps and warpAffine
+ * (tests/test_reference_pins.py, tools/record_reference_cases.md).  Also by the
+ * reference's in-tree known-answer checks
+ * (modules/imgproc/test/test_filter.cpp:2298-2304) and the reference tests' own
+ * acceptance criteria, restated in tests/ (see DESIGN.md §6).
  *
  * Each function cites the reference file:line whose behaviour it restates.
  */

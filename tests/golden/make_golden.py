@@ -2,8 +2,9 @@
 
 These fixtures pin the in-repo synthetic sequence (opencv_amd/csrc/synth_spec.h)
 so that any change to the generator is caught.  They are produced by the CPU
-oracle (oracle/), NOT by the reference — the reference cannot be built here
-(DESIGN.md §Oracle).
+oracle (oracle/), NOT by the reference: the sequence is this project's own.
+(What the reference itself returns is recorded in golden/reference_*.npz by
+tools/record_reference_cases.py)
 
     python tests/golden/make_golden.py
 """

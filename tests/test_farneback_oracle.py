@@ -1,9 +1,10 @@
 """CPU checks of the Farneback oracle (oracle/farneback_oracle.c): known answers
 the reference's algorithm must reproduce.  The reference's own Farneback
 fixtures (opencv_extra rubberwhale1/2.png, video/test/test_optflowgf.cpp) are
-not vendored, so the restatement is pinned by these identities and by its
-line-by-line citations (parity of the full flow field against the reference
-is unpinned)."""
+not vendored; the full flow field of both variants is pinned bit for bit to
+outputs recorded from the reference binaries with AVX2 disabled, the state the
+oracle models (tests/test_reference_pins.py).  These identities
+check the stages on their own."""
 import numpy as np
 import pytest
 

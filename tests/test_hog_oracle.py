@@ -5,8 +5,8 @@ The resize is pinned to the reference's own closed form: Resize_Bitexact.Linear8
 eval4's 8.8 fixed-point formula with zero difference; it is restated here and
 run over the test's size table.  The HOG stages are checked by identities
 (gradient magnitude / angle, L2-Hys norms, SVM score = rho + <descriptor, w>,
-grouping).  Parity of the full detector against the reference binaries is
-unpinned: its HOG tests read opencv_extra images."""
+grouping).  The full detector is pinned to outputs recorded from the reference
+binaries (default dispatch) in tests/test_reference_pins.py."""
 import numpy as np
 import pytest
 

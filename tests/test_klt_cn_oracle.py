@@ -4,8 +4,9 @@ CPU calcOpticalFlowPyrLK on interleaved cn-channel u8 frames
 :178-695 LKTrackerInvoker over winW*cn window elements; pyrDown_ per channel,
 imgproc/src/pyramids.cpp:746-790).
 
-No reference-produced multi-channel vectors exist here, so the cn-generic code
-is pinned to the one-channel oracle (itself pinned, tests/test_oracle.py) by
+The cn-generic code is pinned bit for bit to 2-, 3- and 4-channel pyramids and
+PyrLK runs recorded from the reference binaries (tests/test_reference_pins.py).
+Here it is also tied to the one-channel oracle (tests/test_oracle.py) by
 identities the reference's arithmetic implies:
   * pyrDown and calcSharrDeriv of an interleaved image are the one-channel
     results of each channel;

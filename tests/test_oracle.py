@@ -1,7 +1,11 @@
 """Pin the CPU oracle (oracle/klt_oracle.c) before trusting it.
 
-The reference cannot be built here and its golden data (opencv_extra) is not
-vendored, so the oracle is checked against:
+The oracle is pinned bit for bit to outputs recorded from a build of the
+reference (pyramids, Scharr planes, PyrLK, GFTT and the corner maps, warpAffine:
+tests/test_reference_pins.py, tests/golden/reference_*.npz, recorded by
+tools/record_reference_cases.py).  The reference's own golden data (opencv_extra)
+is not vendored; this file adds the checks that need no
+recording, against:
   * the reference's in-tree known-answer test      test_filter.cpp:2298-2304
   * the reference tests' own independent validators, restated in numpy:
       pyrDown  vs filter2D(kernel/256, REFLECT_101) + decimation, tol 1

@@ -1,0 +1,402 @@
+#!/usr/bin/env python3
+"""Records the real reference (buildOpticalFlowPyramid, calcOpticalFlowPyrLK,
+goodFeaturesToTrack, cornerMinEigenVal / cornerHarris, warpAffine,
+calcOpticalFlowFarneback, HOGDescriptor) on the cases of tests/_reference_cases.py
+into tests/golden/reference_<op>.npz, through tools/reference_driver.cpp (how to
+build it: tools/record_reference_cases.md).
+
+    python tools/record_reference_cases.py /path/to/reference_driver [op ...] [--out DIR]
+
+Every case runs twice, in child processes: `default` (the reference's own
+runtime dispatch) and `noavx2` (OPENCV_CPU_DISABLE=AVX2,AVX512_SKX in the
+child's environment only).  The driver prints checkHardwareSupport; a run whose
+flags do not show the intended state is an error, so a host without AVX2 cannot
+record.  Where the two recordings are byte-identical one copy is stored
+(state "both"); this is asserted for the pyramid, PyrLK and warpAffine.  Where
+they differ, the state the oracle models is stored in full, and for the other
+one: whether the integer-valued results were equal (and those results where
+they were not), the share of equal 32-bit words and the largest absolute
+difference, per case.  The script prints that
+summary as the table kept in tools/record_reference_cases.md.
+
+Nothing in the test suite runs this; the fixtures are committed."""
+import io
+import os
+import subprocess
+import sys
+import tempfile
+import zipfile
+import zlib
+
+import numpy as np
+
+ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+sys.path.insert(0, os.path.join(ROOT, "tests"))
+import _oracle as O  # noqa: E402
+import _reference_cases as RC  # noqa: E402
+
+LIMIT = 256 * 1024
+STATES = ("default", "noavx2")
+# the state each oracle file models where the two differ (README, numerics)
+MODELLED = {"pyramid": "both", "pyrlk": "both", "warpaffine": "both", "gftt": "noavx2", "cornermaps": "noavx2",
+            "farneback": "noavx2", "farneback_box": "noavx2", "hog": "default"}
+
+
+class Driver:
+    def __init__(self, path, state, tmp):
+        self.path, self.state, self.tmp = path, state, tmp
+        self.env = {k: v for k, v in os.environ.items() if k != "OPENCV_CPU_DISABLE"}
+        if state == "noavx2":
+            self.env["OPENCV_CPU_DISABLE"] = "AVX2,AVX512_SKX"
+
+    def run(self, op, files, **kw):
+        """files: name -> array written raw and passed as name=<path>.  Returns
+        (the driver's output lines after the flags line, reader(name, dtype))."""
+        args = []
+        for name, arr in files.items():
+            p = os.path.join(self.tmp, f"in.{name}")
+            np.ascontiguousarray(arr).tofile(p)
+            args.append(f"{name}={p}")
+        args += [f"{k}={v!r}" if isinstance(v, float) else f"{k}={v}" for k, v in kw.items()]
+        prefix = os.path.join(self.tmp, "out")
+        txt = subprocess.run([self.path, op, prefix, *args], check=True, capture_output=True, text=True,
+                             env=self.env).stdout.splitlines()
+        flags = dict(kv.split("=") for kv in txt[0].split())
+        want = "1" if self.state == "default" else "0"
+        if flags["AVX2"] != want or flags["SSE4_1"] != "1":
+            raise SystemExit(f"state {self.state}: the driver reports {txt[0]}")
+        return txt[1:], lambda name, dt: np.fromfile(f"{prefix}.{name}", dt)
+
+
+def img_kw(img):
+    return dict(w=img.shape[1], h=img.shape[0], cn=1 if img.ndim == 2 else img.shape[2])
+
+
+# Each recorder returns (cases, extra): cases a list of (ints, floats), two dicts
+# name -> array of one case's integer-valued and float results; extra: arrays
+# that describe the cases (the same in both states).
+
+def rec_pyramid(d):
+    cases, meta = [], []
+    for w, h, cn, win, maxl, seed in RC.PYR_CASES:
+        img = RC.noise(w, h, cn, seed)
+        out, rd = d.run("pyr", dict(a=img), **img_kw(img), winw=win[0], winh=win[1], maxl=maxl)
+        n = int(out[0].split()[1])
+        ints = {}
+        for i in range(n):
+            lw, lh = map(int, out[1 + i].split())
+            ints[f"L{i}"] = rd(f"L{i}", np.uint8).reshape(lh, lw * cn)
+            ints[f"D{i}"] = rd(f"D{i}", np.int16).reshape(lh, lw * cn * 2)
+        cases.append((ints, {}))
+        meta.append((w, h, cn, win[0], win[1], maxl, seed, n))
+    return cases, dict(meta=np.array(meta, np.int32))
+
+
+def lk_points(d):
+    """per pair: the frame's own GFTT corners plus the fixed edge points, and an initial guess"""
+    extra = {}
+    for pair in RC.LK_PAIRS:
+        a, _ = RC.lk_pair(pair, 1)
+        _, rd = d.run("gftt", dict(a=a), **img_kw(a), maxc=150, ql=0.01, md=5.0, block=3, harris=0, k=0.04)
+        pts = np.concatenate([rd("c", np.float32).reshape(-1, 2), RC.LK_EDGE_POINTS])
+        n = RC.noise(len(pts), 1, 2, 55).astype(np.float32).reshape(-1, 2)
+        extra[f"pts_{pair}"] = pts
+        extra[f"init_{pair}"] = pts + (n - np.float32(128)) / np.float32(64)  # a guess within 2 px
+    return extra
+
+
+def rec_pyrlk(d, extra):
+    cases = []
+    for pair, cn, win, lev, flags, want_err in RC.lk_cases():
+        a, b = RC.lk_pair(pair, cn)
+        pts = extra[f"pts_{pair}"]
+        files = dict(a=a, b=b, pts=pts)
+        if flags & RC.OPTFLOW_USE_INITIAL_FLOW:
+            files["init"] = extra[f"init_{pair}"]
+        _, rd = d.run("lk", files, **img_kw(a), winw=win[0], winh=win[1], maxl=lev, flags=flags, n=len(pts),
+                      err=want_err)
+        floats = dict(q=rd("q", np.float32).reshape(-1, 2))
+        if want_err:
+            floats["err"] = rd("err", np.float32)
+        cases.append((dict(st=rd("st", np.uint8)), floats))
+    return cases, extra
+
+
+def lk_exact_order_check(cases, extra):
+    """O.lk(..., accum=ACCUM_EXACT), the order the kernels are proven equal to,
+    meets test_gpu_klt.assert_tolerance's default bars against every recorded
+    case; returns per pair the points that spoil a case (to be replaced)."""
+    from test_gpu_klt import assert_tolerance
+
+    spoil = {p: set() for p in RC.LK_PAIRS}
+    for (pair, cn, win, lev, flags, want_err), (ints, floats) in zip(RC.lk_cases(), cases):
+        a, b = RC.lk_pair(pair, cn)
+        Pa, Pb = O.Pyramid(a, win, lev, RC.lk_pad(win)), O.Pyramid(b, win, lev, RC.lk_pad(win))
+        init = extra[f"init_{pair}"] if flags & RC.OPTFLOW_USE_INITIAL_FLOW else None
+        ex = O.lk(Pa, Pb, extra[f"pts_{pair}"], win, lev, 30, 0.01, flags, accum=O.ACCUM_EXACT, init=init,
+                  want_err=bool(want_err))
+        try:
+            assert_tolerance(ex, (floats["q"], ints["st"]))
+        except AssertionError:
+            both = (ex[1] == 1) & (ints["st"] == 1)
+            far = both & (np.abs(ex[0] - floats["q"]).max(1) > 1e-2)
+            spoil[pair] |= set(np.flatnonzero((ex[1] != ints["st"]) | far).tolist())
+    return spoil
+
+
+def rec_gftt(d):
+    cases, meta = [], []
+    for r, maxc, ql, md, block, harris in RC.gftt_cases():
+        roi = RC.gftt_roi(r)
+        _, rd = d.run("gftt", dict(a=roi), **img_kw(roi), maxc=maxc, ql=ql, md=md, block=block, harris=harris,
+                      k=RC.HARRIS_K)
+        c = rd("c", np.float32).reshape(-1, 2)
+        assert np.array_equal(c, c.astype(np.uint16))  # corners are pixel positions: stored as uint16, exactly
+        cases.append((dict(c=c.astype(np.uint16)), {}))
+        meta.append((r, maxc, block, harris))
+    return cases, dict(meta=np.array(meta, np.int32))
+
+
+def rec_cornermaps(d):
+    cases, meta = [], []
+    for w, h, seed in RC.CMAP_SHAPES:
+        img = RC.noise(w, h, 1, seed)
+        for block, harris in RC.CMAP_MODES:
+            _, rd = d.run("cmap", dict(a=img), **img_kw(img), block=block, harris=harris, k=RC.HARRIS_K)
+            cases.append(({}, dict(e=rd("e", np.float32).reshape(h, w))))
+            meta.append((w, h, seed, block, harris))
+    return cases, dict(meta=np.array(meta, np.int32))
+
+
+def warp_table():
+    """(flags, border, bval, sw, sh, dw, dh, M) per case: 4 interpolations x 6 borders x
+    the inverse flag on matrices drawn from a fixed seed, then the degenerate matrices"""
+    rng = np.random.default_rng(20261019)
+    rows, i = [], 0
+    for inter in range(4):
+        for border in range(6):
+            for inv in (0, O.WARP_INVERSE_MAP):
+                (sw, sh), (dw, dh) = RC.WARP_SRC[i % len(RC.WARP_SRC)], RC.WARP_DST[i % len(RC.WARP_DST)]
+                ang, sc = np.deg2rad(rng.uniform(-180, 180)), rng.uniform(0.4, 2.0)
+                al, be = np.cos(ang) * sc, np.sin(ang) * sc
+                M = np.array([[al, be, (1 - al) * sw / 2 - be * sh / 2], [-be, al, be * sw / 2 + (1 - al) * sh / 2]])
+                M[:, 2] += rng.uniform(-10, 10, 2)
+                rows.append((inter | inv, border, int(rng.integers(0, 256)), sw, sh, dw, dh, M))
+                i += 1
+    for M in RC.WARP_DEGENERATE:
+        for inter in (O.INTER_LINEAR, O.INTER_CUBIC):
+            rows.append((inter, O.BORDER_CONSTANT, 3, 96, 61, 70, 50, np.asarray(M, np.float64)))
+    return rows
+
+
+def rec_warpaffine(d):
+    cases, meta, mats = [], [], []
+    for i, (flags, border, bval, sw, sh, dw, dh, M) in enumerate(warp_table()):
+        src, dst = RC.warp_inputs(i, sw, sh, dw, dh)
+        _, rd = d.run("warp", dict(a=src, m=M, dst=dst), w=sw, h=sh, dw=dw, dh=dh, flags=flags, border=border,
+                      bval=bval)
+        cases.append((dict(w=rd("w", np.uint8).reshape(dh, dw)), {}))
+        meta.append((flags, border, bval, sw, sh, dw, dh))
+        mats.append(M)
+    return cases, dict(meta=np.array(meta, np.int32), M=np.array(mats, np.float64))
+
+
+def rec_farneback(d, table=None):
+    cases, meta = [], []
+    for w, h, ps, pn, ws, flags, use_init in table or RC.FB_CASES:
+        a, b = RC.fb_pair(w, h)
+        files = dict(a=a, b=b)
+        if use_init:
+            files["init"] = RC.fb_init(w, h)
+        _, rd = d.run("fb", files, w=w, h=h, ps=float(ps), lv=RC.FB_LEVELS, ws=ws, it=RC.FB_ITERS, pn=pn,
+                      sg=RC.fb_sigma(pn), flags=flags | (O.OPTFLOW_USE_INITIAL_FLOW if use_init else 0))
+        cases.append(({}, dict(f=rd("f", np.float32).reshape(h, w * 2))))
+        meta.append((w, h, int(round(ps * 10)), pn, ws, flags, use_init))
+    return cases, dict(meta=np.array(meta, np.int32))
+
+
+def rec_farneback_box(d):
+    return rec_farneback(d, RC.FB_BOX_CASES)
+
+
+def hog_thresholds(d):
+    """per detection case a hit threshold (a multiple of 1/64) at which detect()
+    and the ungrouped detectMultiScale() both return between 10 and 500 windows:
+    the lowest of a few quantiles of the image's window scores that does"""
+    hits = []
+    for win, cn, _ in RC.HOG_DET_CASES:
+        img = RC.hog_image(160, 256, cn, 300 + win[0] + cn)
+        _, rd = d.run("hogdet", dict(a=img), **img_kw(img), win=win[0], hit=-1e9, group=0)
+        scores = rd("wt", np.float64)
+        for q in (0.5, 2 / 3, 0.8, 0.9, 0.95):
+            hit = float(np.floor(np.quantile(scores, q) * 64) / 64)
+            out, _ = d.run("hogdet", dict(a=img), **img_kw(img), win=win[0], hit=hit, group=0)
+            nwin, nrect = int(out[0].split()[1]), int(out[0].split()[3])
+            if 10 <= nwin <= 500 and 10 <= nrect <= 500:
+                break
+        else:
+            raise SystemExit(f"hog {win} cn {cn}: no threshold gives 10 to 500 windows")
+        hits.append(hit)
+    return np.array(hits, np.float64)
+
+
+def rec_hog(d, extra):
+    cases = []
+    for i, (w, h, cn, gamma, signed, _) in enumerate(RC.HOG_GRAD_CASES):
+        img = RC.hog_grad_image(i)
+        _, rd = d.run("hoggrad", dict(a=img), **img_kw(img), gamma=gamma, signed=signed)
+        cases.append((dict(qa=rd("qa", np.uint8).reshape(h, w * 2)), dict(g=rd("g", np.float32).reshape(h, w * 2))))
+    for (win, cn, group), hit in zip(RC.HOG_DET_CASES, extra["hit"]):
+        img = RC.hog_image(160, 256, cn, 300 + win[0] + cn)
+        _, rd = d.run("hogdet", dict(a=img), **img_kw(img), win=win[0], hit=float(hit), group=group)
+        loc, r = rd("loc", np.int32).reshape(-1, 2), rd("r", np.int32).reshape(-1, 4)
+        if not (10 <= len(loc) <= 500 and (len(r) >= 1 if group else 10 <= len(r) <= 500)):
+            raise SystemExit(f"hog {win} cn {cn} group {group}: {len(loc)} windows, {len(r)} rects at {hit}")
+        svm = rd("svm", np.float32)
+        mine = np.fromfile(os.path.join(ROOT, "opencv_amd", "data", f"hog_people_{win[0]}x{win[1]}.f32"), np.float32)
+        if not np.array_equal(svm.view(np.uint32), mine.view(np.uint32)):
+            raise SystemExit(f"the {win} detector differs from opencv_amd/data")
+        extra[f"svm_crc_{win[0]}"] = np.array([zlib.crc32(svm.tobytes()), svm.size], np.uint32)
+        cases.append((dict(loc=loc, r=r), dict(wt=rd("wt", np.float64), rw=rd("rw", np.float64))))
+    return cases, extra
+
+
+def words(a):
+    return np.ascontiguousarray(a).reshape(-1).view(np.uint32)
+
+
+def merge(op, rec, whole_limit):
+    """rec: state -> (cases, extra).  Returns (arrays, table rows)."""
+    modelled = MODELLED[op]
+    (c0, extra), (c1, extra1) = rec["default"], rec["noavx2"]
+    assert extra.keys() == extra1.keys() and all(np.array_equal(extra[k], extra1[k]) for k in extra), op
+    n = len(c0)
+    ints_eq, share, maxabs = np.ones(n, np.uint8), np.ones(n), np.zeros(n)
+    for i, ((i0, f0), (i1, f1)) in enumerate(zip(c0, c1)):
+        ints_eq[i] = all(i0[k].shape == i1[k].shape and np.array_equal(i0[k], i1[k]) for k in i0)
+        same = [f0[k].shape == f1[k].shape for k in f0]
+        if f0 and all(same):
+            eq = np.concatenate([words(f0[k]) == words(f1[k]) for k in f0])
+            share[i] = eq.mean() if eq.size else 1.0
+            maxabs[i] = max([float(np.abs(f0[k].astype(np.float64) - f1[k]).max()) for k in f0 if f0[k].size] or [0.0])
+        elif f0:
+            share[i], maxabs[i] = 0.0, np.inf  # another number of results
+    identical = bool(ints_eq.all() and (share == 1.0).all())
+    if modelled == "both" and not identical:
+        raise SystemExit(f"{op}: the two dispatch states differ: ints {ints_eq.tolist()} share {share.tolist()}")
+    state = "both" if identical else modelled
+    keep, other = (c1, c0) if state == "noavx2" else (c0, c1)
+    arrays = {k: v for k, v in extra.items()}
+    for i, (ints, floats) in enumerate(keep):
+        for k, v in {**ints, **floats}.items():
+            arrays[f"{i}_{k}"] = RC.pack(v, whole_limit)
+        if not ints_eq[i]:  # the other state's integer-valued results, where they are not the same
+            for k, v in other[i][0].items():
+                arrays[f"other_{i}_{k}"] = RC.pack(v, whole_limit)
+    arrays["state"] = np.array(state)
+    arrays["other_ints_equal"], arrays["other_share"], arrays["other_maxabs"] = ints_eq, share, maxabs
+    return arrays, (state, ints_eq, share, maxabs)
+
+
+RECORDERS = {"pyramid": rec_pyramid, "pyrlk": rec_pyrlk, "gftt": rec_gftt, "cornermaps": rec_cornermaps,
+             "warpaffine": rec_warpaffine, "farneback": rec_farneback, "farneback_box": rec_farneback_box,
+             "hog": rec_hog}
+# bytes up to which an output is stored whole (tests/_reference_cases.py: WHOLE_LIMIT).  The kernels are
+# compared with the box Farneback flows within a tolerance, so all six stay whole (about 7 KB under LIMIT)
+WHOLE = {"farneback": 20480, "farneback_box": 72800, "pyrlk": 1 << 20, "gftt": 1 << 20, "hog": 16384}
+
+
+def save(path, arrays):
+    """np.savez_compressed with fixed member times, so a re-recording gives the same file"""
+    with zipfile.ZipFile(path, "w", zipfile.ZIP_DEFLATED) as z:
+        for name, a in arrays.items():
+            buf = io.BytesIO()
+            np.lib.format.write_array(buf, np.asanyarray(a), allow_pickle=False)
+            z.writestr(zipfile.ZipInfo(name + ".npy", date_time=(1980, 1, 1, 0, 0, 0)), buf.getvalue(),
+                       zipfile.ZIP_DEFLATED)
+
+
+def case_label(op, i):
+    if op == "pyrlk":
+        pair, cn, win, lev, flags, err = RC.lk_cases()[i]
+        return f"{pair} cn {cn} win {win[0]}x{win[1]} levels {lev} flags {flags}" + ("" if err else " no err")
+    if op == "gftt":
+        r, maxc, ql, md, block, harris = RC.gftt_cases()[i]
+        return f"roi {r} ({maxc}, {ql}, {md}) block {block}" + (" harris" if harris else "")
+    if op == "cornermaps":
+        w, h, _ = RC.CMAP_SHAPES[i // len(RC.CMAP_MODES)]
+        block, harris = RC.CMAP_MODES[i % len(RC.CMAP_MODES)]
+        return f"{h}x{w} block {block} " + ("harris" if harris else "minEigenVal")
+    if op in ("farneback", "farneback_box"):
+        w, h, ps, pn, ws, flags, init = (RC.FB_CASES if op == "farneback" else RC.FB_BOX_CASES)[i]
+        return f"{w}x{h} scale {ps} polyN {pn} win {ws} " + ("gaussian" if flags else "box") + (" init" if init else "")
+    if op == "hog":
+        g = len(RC.HOG_GRAD_CASES)
+        if i < g:
+            return "computeGradient {}x{} cn {} gamma {} signed {}".format(*RC.HOG_GRAD_CASES[i])
+        win, cn, group = RC.HOG_DET_CASES[i - g]
+        return f"detect / detectMultiScale {win[0]}x{win[1]} cn {cn} group {group}"
+    return f"case {i}"
+
+
+def main():
+    argv = sys.argv[1:]
+    out_dir = os.path.join(ROOT, "tests", "golden")
+    if "--out" in argv:
+        k = argv.index("--out")
+        out_dir = argv[k + 1]
+        del argv[k:k + 2]
+    driver, ops = argv[0], argv[1:] or list(RECORDERS)
+    table = []
+    with tempfile.TemporaryDirectory() as tmp:
+        drv = {s: Driver(driver, s, tmp) for s in STATES}
+        for op in ops:
+            rec = {}
+            if op == "pyrlk":
+                extra = lk_points(drv["noavx2"])
+                assert all(np.array_equal(v, lk_points(drv["default"])[k]) for k, v in extra.items())
+                for _ in range(8):
+                    rec = {s: rec_pyrlk(drv[s], dict(extra)) for s in STATES}
+                    spoil = lk_exact_order_check(rec["default"][0], extra)
+                    if not any(spoil.values()):
+                        break
+                    for pair, idx in spoil.items():  # other points: drop the ones that spoil a case
+                        if not idx:
+                            continue
+                        n_gftt = len(extra[f"pts_{pair}"]) - len(RC.LK_EDGE_POINTS)
+                        assert all(i < n_gftt for i in idx), (pair, "an edge point misses the bars", sorted(idx))
+                        keep = np.array([i not in idx for i in range(len(extra[f"pts_{pair}"]))])
+                        print(f"pyrlk: {pair}: dropping points {sorted(idx)}")
+                        for k in (f"pts_{pair}", f"init_{pair}"):
+                            extra[k] = extra[k][keep]
+                else:
+                    raise SystemExit("pyrlk: no point set meets the bars")
+                assert all(len(extra[f"pts_{p}"]) <= 400 for p in RC.LK_PAIRS)
+            elif op == "hog":
+                hit = hog_thresholds(drv["default"])
+                rec = {s: rec_hog(drv[s], dict(hit=hit)) for s in STATES}
+            else:
+                rec = {s: RECORDERS[op](drv[s]) for s in STATES}
+            arrays, row = merge(op, rec, WHOLE.get(op, RC.WHOLE_LIMIT))
+            path = os.path.join(out_dir, f"reference_{op}.npz")
+            save(path, arrays)
+            size = os.path.getsize(path)
+            print(f"{path}: {len(rec['default'][0])} cases, state {row[0]}, {size} bytes")
+            assert size <= LIMIT, (op, size)
+            table.append((op, *row))
+    print("\n| fixture | case | stored state | integer results equal in the other state | equal 32-bit words | "
+          "largest difference |\n|---|---|---|---|---|---|")
+    for op, state, ints_eq, share, maxabs in table:
+        if state == "both":
+            print(f"| {op} | all {len(share)} | both | yes | 100 % | 0 |")
+            continue
+        same = ints_eq.astype(bool) & (share == 1.0)
+        if same.any():
+            print(f"| {op} | {int(same.sum())} cases of {len(share)} | {state} | yes | 100 % | 0 |")
+        for i in np.flatnonzero(~same):
+            print(f"| {op} | {case_label(op, i)} | {state} | {'yes' if ints_eq[i] else 'NO'} | "
+                  f"{100 * share[i]:.1f} % | {maxabs[i]:.3g} |")
+
+
+if __name__ == "__main__":
+    main()

@@ -1,0 +1,190 @@
+// reference_driver.cpp — records the reference's CPU functions on raw files for
+// tests/golden/reference_<op>.npz (see tools/record_reference_cases.md).
+// Links against a scratch build of the reference's core, imgproc, video and
+// objdetect modules; nothing in the test suite builds or runs it.
+//
+//   reference_driver <op> <out-prefix> key=value ...
+//
+// Images are raw 8-bit files (rows of w * cn bytes); every output goes to
+// <out-prefix>.<name> as raw little-endian data.  The first line printed is the
+// runtime dispatch state, "SSE4_1=. AVX=. AVX2=. FMA3=."; the caller checks it.
+//
+//   pyr   a= w= h= cn= winw= winh= maxl=           -> L<i> (u8), D<i> (i16, 2cn per pixel); prints the level sizes
+//   lk    a= b= w= h= cn= winw= winh= maxl= flags= pts= n= [init=] err=0|1
+//                                                  -> q (f32 pairs), st (u8), err (f32, if err=1)
+//   gftt  a= w= h= maxc= ql= md= block= harris= k= -> c (f32 pairs); prints the count
+//   cmap  a= w= h= block= harris= k=               -> e (f32): cornerMinEigenVal / cornerHarris, ksize 3
+//   warp  a= w= h= m= (6 doubles, raw) dst= dw= dh= flags= border= bval=   -> w (u8)
+//   fb    a= b= w= h= ps= lv= ws= it= pn= sg= flags= [init=]               -> f (f32 pairs)
+//   hoggrad a= w= h= cn= gamma= signed=            -> g (f32 pairs), qa (u8 pairs)
+//   hogdet  a= w= h= cn= win=64|48 hit= group=     -> loc (i32 pairs), wt (f64), r (i32 x4), rw (f64), svm (f32)
+#include <cstdio>
+#include <cstdlib>
+#include <map>
+#include <stdexcept>
+#include <string>
+#include <vector>
+
+#include <opencv2/core.hpp>
+#include <opencv2/imgproc.hpp>
+#include <opencv2/objdetect.hpp>
+#include <opencv2/video/tracking.hpp>
+
+using namespace cv;
+
+static std::map<std::string, std::string> g_args;
+
+static const std::string& arg(const std::string& k)
+{
+    std::map<std::string, std::string>::const_iterator it = g_args.find(k);
+    if (it == g_args.end()) throw std::runtime_error("missing argument " + k);
+    return it->second;
+}
+static bool has(const std::string& k) { return g_args.count(k) != 0; }
+static int iarg(const std::string& k) { return std::atoi(arg(k).c_str()); }
+static double darg(const std::string& k) { return std::strtod(arg(k).c_str(), NULL); }
+
+static void rd(const std::string& path, void* dst, size_t bytes)
+{
+    FILE* f = std::fopen(path.c_str(), "rb");
+    if (!f || std::fread(dst, 1, bytes, f) != bytes) throw std::runtime_error("short read of " + path);
+    std::fclose(f);
+}
+
+static void wr(const std::string& out, const char* name, const void* src, size_t bytes)
+{
+    FILE* f = std::fopen((out + "." + name).c_str(), "wb");
+    if (!f || std::fwrite(src, 1, bytes, f) != bytes) throw std::runtime_error("cannot write " + out + "." + name);
+    std::fclose(f);
+}
+
+static void wr(const std::string& out, const std::string& name, const Mat& m)
+{
+    Mat c = m.isContinuous() ? m : m.clone();
+    wr(out, name.c_str(), c.data, c.total() * c.elemSize());
+}
+
+static Mat image(const std::string& key, int w, int h, int cn)
+{
+    Mat m(h, w, CV_8UC(cn));
+    rd(arg(key), m.data, (size_t)w * h * cn);
+    return m;
+}
+
+static int run(const std::string& op, const std::string& out)
+{
+    const int w = iarg("w"), h = iarg("h"), cn = has("cn") ? iarg("cn") : 1;
+    Mat a = image("a", w, h, cn);
+    if (op == "pyr") {
+        std::vector<Mat> pyr;
+        int top = buildOpticalFlowPyramid(a, pyr, Size(iarg("winw"), iarg("winh")), iarg("maxl"), true);
+        std::printf("levels %d\n", top + 1);
+        for (int i = 0; i <= top; ++i) {
+            std::printf("%d %d\n", pyr[2 * i].cols, pyr[2 * i].rows);
+            wr(out, "L" + std::to_string(i), pyr[2 * i]);
+            wr(out, "D" + std::to_string(i), pyr[2 * i + 1]);
+        }
+    } else if (op == "lk") {
+        Mat b = image("b", w, h, cn);
+        const int n = iarg("n"), flags = iarg("flags");
+        std::vector<Point2f> p(n), q;
+        rd(arg("pts"), p.data(), sizeof(Point2f) * n);
+        if (has("init")) {
+            q.resize(n);
+            rd(arg("init"), q.data(), sizeof(Point2f) * n);
+        }
+        std::vector<uchar> st;
+        std::vector<float> err;
+        const Size win(iarg("winw"), iarg("winh"));
+        const TermCriteria crit(TermCriteria::COUNT + TermCriteria::EPS, 30, 0.01);
+        if (iarg("err"))
+            calcOpticalFlowPyrLK(a, b, p, q, st, err, win, iarg("maxl"), crit, flags, 1e-4);
+        else
+            calcOpticalFlowPyrLK(a, b, p, q, st, noArray(), win, iarg("maxl"), crit, flags, 1e-4);
+        wr(out, "q", q.data(), sizeof(Point2f) * n);
+        wr(out, "st", st.data(), n);
+        if (iarg("err")) wr(out, "err", err.data(), sizeof(float) * n);
+    } else if (op == "gftt") {
+        std::vector<Point2f> c;
+        goodFeaturesToTrack(a, c, iarg("maxc"), darg("ql"), darg("md"), noArray(), iarg("block"), iarg("harris") != 0,
+                            darg("k"));
+        std::printf("corners %d\n", (int)c.size());
+        wr(out, "c", c.data(), sizeof(Point2f) * c.size());
+    } else if (op == "cmap") {
+        Mat e;
+        if (iarg("harris"))
+            cornerHarris(a, e, iarg("block"), 3, darg("k"));
+        else
+            cornerMinEigenVal(a, e, iarg("block"), 3);
+        wr(out, "e", e);
+    } else if (op == "warp") {
+        double m[6];
+        rd(arg("m"), m, sizeof m);
+        const int dw = iarg("dw"), dh = iarg("dh");
+        Mat M(2, 3, CV_64F, m), d(dh, dw, CV_8UC1);
+        rd(arg("dst"), d.data, (size_t)dw * dh);
+        const uchar* before = d.data;
+        warpAffine(a, d, M, Size(dw, dh), iarg("flags"), iarg("border"), Scalar(iarg("bval")));
+        if (d.data != before) throw std::runtime_error("warpAffine reallocated the destination");
+        wr(out, "w", d);
+    } else if (op == "fb") {
+        Mat b = image("b", w, h, 1), flow;
+        if (has("init")) {
+            flow.create(h, w, CV_32FC2);
+            rd(arg("init"), flow.data, (size_t)w * h * 8);
+        }
+        calcOpticalFlowFarneback(a, b, flow, darg("ps"), iarg("lv"), iarg("ws"), iarg("it"), iarg("pn"), darg("sg"),
+                                 iarg("flags"));
+        wr(out, "f", flow);
+    } else if (op == "hoggrad") {
+        HOGDescriptor hog;
+        hog.gammaCorrection = iarg("gamma") != 0;
+        hog.signedGradient = iarg("signed") != 0;
+        Mat grad, qa;
+        hog.computeGradient(a, grad, qa, Size(), Size());
+        wr(out, "g", grad);
+        wr(out, "qa", qa);
+    } else if (op == "hogdet") {
+        const bool small = iarg("win") == 48;
+        HOGDescriptor hog(small ? Size(48, 96) : Size(64, 128), Size(16, 16), Size(8, 8), Size(8, 8), 9);
+        std::vector<float> svm = small ? HOGDescriptor::getDaimlerPeopleDetector()
+                                       : HOGDescriptor::getDefaultPeopleDetector();
+        hog.gammaCorrection = true;  // the default constructor's value; this constructor's default is false
+        hog.setSVMDetector(svm);
+        std::vector<Point> loc;
+        std::vector<double> wt, rw;
+        std::vector<Rect> r;
+        hog.detect(a, loc, wt, darg("hit"), Size(8, 8), Size(0, 0));
+        hog.detectMultiScale(a, r, rw, darg("hit"), Size(8, 8), Size(), 1.05, iarg("group"));
+        std::printf("windows %d rects %d\n", (int)loc.size(), (int)r.size());
+        wr(out, "loc", loc.data(), sizeof(Point) * loc.size());
+        wr(out, "wt", wt.data(), sizeof(double) * wt.size());
+        wr(out, "r", r.data(), sizeof(Rect) * r.size());
+        wr(out, "rw", rw.data(), sizeof(double) * rw.size());
+        wr(out, "svm", svm.data(), sizeof(float) * svm.size());
+    } else {
+        throw std::runtime_error("unknown operation " + op);
+    }
+    return 0;
+}
+
+int main(int argc, char** argv)
+{
+    if (argc < 3) return 2;
+    for (int i = 3; i < argc; ++i) {
+        std::string kv = argv[i];
+        size_t eq = kv.find('=');
+        if (eq == std::string::npos) return 2;
+        g_args[kv.substr(0, eq)] = kv.substr(eq + 1);
+    }
+    setNumThreads(1);
+    std::printf("SSE4_1=%d AVX=%d AVX2=%d FMA3=%d\n", (int)checkHardwareSupport(CV_CPU_SSE4_1),
+                (int)checkHardwareSupport(CV_CPU_AVX), (int)checkHardwareSupport(CV_CPU_AVX2),
+                (int)checkHardwareSupport(CV_CPU_FMA3));
+    try {
+        return run(argv[1], argv[2]);
+    } catch (const std::exception& e) {
+        std::fprintf(stderr, "reference_driver: %s\n", e.what());
+        return 1;
+    }
+}
