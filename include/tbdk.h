@@ -108,12 +108,10 @@ int tbdk_ctx_destroy(tbdk_ctx* ctx);
  *       eigenvalue strips as a fresh-start mismatch, forcing the re-walk
  *       rounds taken when a segment's fresh start differs from the
  *       reference's running box-filter sum (results equal).
- *   "pyr_fuse" (0/1/2, default 1): tbdk_pyr_build of a u8 pyramid: 1
+ *   "pyr_fuse" (0/1, default 1): tbdk_pyr_build of a u8 pyramid: 1
  *       computes level 0's padded copy and level 1 in one launch, then one
- *       launch per level; 2 computes levels 0, 1 and 2 in one tiled launch (the
- *       frame read once through LDS; pyramids whose level pads exceed size - 2
- *       take 1; measured slower, kept for A/B runs); 0: one launch per level
- *       (results equal).  fp16 / fp32 pyramids: >= 1 builds L levels in L
+ *       launch per level; 0: one launch per level
+ *       (results equal).  fp16 / fp32 pyramids: 1 builds L levels in L
  *       role-split launches (level 0's copy, level 1 and level 0's Scharr
  *       plane from the frame, then level i and plane i-1 from level i-1);
  *       0 takes one launch per level and one for every plane (results equal).
@@ -178,14 +176,6 @@ int tbdk_ctx_set_option(tbdk_ctx* ctx, const char* name, int64_t value);
  *       system-scope flag in pinned memory that the host polls, instead of an
  *       event recorded behind the fit (whose marker held the next frame's
  *       pyramid back; results equal).
- *   "tbd_early_order" (0/1/2, default 0): where a step launches its early
- *       GFTT (and, tbd_gftt_ahead, the next frame's): 0 first, 1 after the
- *       critical refreshed-set PyrLK (its host setup no longer delays that
- *       launch, and the PyrLK waves are dispatched ahead of the GFTT's), 2 after
- *       the fit and the next frame's pyramid, before the host waits for the fit
- *       (results equal).
- *   "tbd_early_prio" (0/1, default 0; taken by tbdk_tbd_create): the early
- *       GFTT's stream at the lowest (0) or highest (1) priority (results equal).
  *   "tbd_pyr_derivs" (0/1, default 0; taken by tbdk_tbd_create): the loop's
  *       pyramids carry Scharr derivative planes and PyrLK reads them instead of
  *       deriving the window's values (results equal; A/B runs).
@@ -211,9 +201,6 @@ int tbdk_ctx_set_option(tbdk_ctx* ctx, const char* name, int64_t value);
  *       GFTT, the next step's refreshed-set PyrLK waits for the early GFTT's
  *       completion directly rather than through the post-tracker stream's
  *       event (results equal).
- *   "tbd_la_defer" (0/1, default 0): the look-ahead PyrLK of the unchanged
- *       sets is launched by the next step right after its critical PyrLK
- *       instead of at the end of its own step (results equal; A/B runs).
  *   "gftt_compact" (0/1, default 1): GFTT with quality <= 1 (blockSize 3,
  *       min-eigenvalue) writes no eigenvalue plane, only its local maxima's
  *       values per strip row (corner lists equal; quality > 1, Harris and other
@@ -225,10 +212,6 @@ int tbdk_ctx_set_option(tbdk_ctx* ctx, const char* name, int64_t value);
  *       a GFTT launched only one step earlier; the step of that frame launches
  *       just the ROIs it misses (re-detection guesses).  The caller's stream
  *       waits for that work before the call returns (results equal).
- *   "tbd_ahead_at" (0/1/2, default 0): where a step launches that ahead GFTT:
- *       0 with its own early GFTT, 1 after its critical PyrLK, 2 just before
- *       the host waits for the fit (never before the step's own early GFTT;
- *       results equal).
  *   "tbd_borrow_l0" (0/1, default 0): inside tbdk_tbd_run the loop's pyramids
  *       take the caller's frames as level 0 (no padded copy; PyrLK reads
  *       windows across a frame's edge by reflect-101 coordinates, the values
@@ -258,10 +241,6 @@ int tbdk_ctx_set_option(tbdk_ctx* ctx, const char* name, int64_t value);
  *       the kept pairs only.  tbdk_frame_metrics: lk_points counts the points
  *       entering the forward pass, klt_points the pairs kept after the check,
  *       lk_iters the forward pass's iterations.
- *   "tbd_async_la" (0/1, default 0; taken by tbdk_tbd_create): the TBD loop's
- *       look-ahead PyrLK launches are issued by a worker thread of the loop
- *       (one more host thread per loop, spinning between frames; results equal;
- *       A/B runs).
  *   "timing_every" (>= 1, default 1): HIP events on a pseudo-random 1/N of the
  *       launches of each kernel selected for timing: launch i (counted per
  *       kernel name from tbdk_timing_enable) is timed iff splitmix64(i) % N == 0

@@ -512,12 +512,8 @@ struct FbIterArgs {
 
 __device__ __forceinline__ float fb_border(int i) { return i < 2 ? 0.14f : 0.4472f; }
 
-// 1: each batch's 2x2 solves run at the top of the next batch, beside its M
-// rows' finish (whose bilinear R1 terms are selected, not branched around);
-// 0: the solve right after the horizontal sums (tuning builds)
-#ifndef TBDK_FB_DEFER
-#define TBDK_FB_DEFER 1
-#endif
+// Each batch's 2x2 solves run at the top of the next batch, beside its M
+// rows' finish (whose bilinear R1 terms are selected, not branched around)
 
 // FarnebackUpdateMatrices at pixel (x, y) (optflowgf.cpp:235-309), in three
 // phases so a strip can keep two rows of loads in flight: A = the pixel's flow
@@ -587,7 +583,6 @@ __device__ __forceinline__ void fb_finish(const FbIterArgs& a, int x, int y, con
     const float dx = A.dx, dy = A.dy;
     const float R00 = A.r0[0], R01 = A.r0[1], R02 = A.r0[2], R03 = A.r0[3], R04 = A.r0[4];
     float r2, r3, r4, r5, r6;
-#if TBDK_FB_DEFER
     // the R1 terms evaluated for every pixel and selected by B.in (same
     // values as the branch), so the finish of interior rows is one basic
     // block the deferred solve can interleave with
@@ -603,25 +598,6 @@ __device__ __forceinline__ void fb_finish(const FbIterArgs& a, int x, int y, con
         r5 = B.in ? (R03 + r[3]) * 0.5f : R03;
         r6 = B.in ? (R04 + r[4]) * 0.25f : R04 * 0.5f;
     }
-#else
-    if (B.in) {
-        const float fx = B.fx, fy = B.fy;
-        const float a00 = (1.f - fx) * (1.f - fy), a01 = fx * (1.f - fy), a10 = (1.f - fx) * fy, a11 = fx * fy;
-        float r[5];
-#pragma unroll
-        for (int c = 0; c < 5; ++c) r[c] = a00 * B.q[c][0] + a01 * B.q[c][1] + a10 * B.q[c][2] + a11 * B.q[c][3];
-        r2 = r[0];
-        r3 = r[1];
-        r4 = (R02 + r[2]) * 0.5f;
-        r5 = (R03 + r[3]) * 0.5f;
-        r6 = (R04 + r[4]) * 0.25f;
-    } else {
-        r2 = r3 = 0.f;
-        r4 = R02;
-        r5 = R03;
-        r6 = R04 * 0.5f;
-    }
-#endif
     r2 = (R00 - r2) * 0.5f;
     r3 = (R01 - r3) * 0.5f;
     r2 += r4 * dy + r6 * dx;
@@ -642,30 +618,18 @@ __device__ __forceinline__ void fb_finish(const FbIterArgs& a, int x, int y, con
     M[4] = r6 * r2 + r5 * r3;
 }
 
-// LDS slot of strip lane l: one pad double every 4, so the horizontal runs
-// (thread q reads lanes 4q..4q+3+2m) hit distinct banks
-//
-// TBDK_FB_W64 (round 6): the horizontal windows read as 8-byte pairs
+// LDS slot of strip lane l.  The horizontal windows are read as 8-byte pairs
 // (ds_read_b64: twice the bytes per LDS cycle of ds_read_b32); the windows
 // start at even columns, so the row is unpadded, and rows (channel, batch
 // row) are kFbStrip + 2 floats apart — an odd number of 8-byte banks — so the
 // 32 lanes of a read group, 16 distinct windows of one row or the tail of one
 // row and the head of the next, hit distinct banks (tools/r06_fb_lds.sh)
-#ifndef TBDK_FB_W64
-#define TBDK_FB_W64 1
-#endif
-#if TBDK_FB_W64
 __device__ __forceinline__ int fb_slot(int l) { return l; }
 constexpr int kFbSlots = kFbStrip + 2;
-#else
-__device__ __forceinline__ int fb_slot(int l) { return l + (l >> 2); }
-constexpr int kFbSlots = kFbStrip + kFbStrip / 4;
-#endif
-// the window values row[l0 .. l0 + NW) (l0 and NW even under TBDK_FB_W64)
+// the window values row[l0 .. l0 + NW) (l0 and NW even)
 template <int NW>
 __device__ __forceinline__ void fb_window(const float* row, int l0, float (&win)[NW])
 {
-#if TBDK_FB_W64
     static_assert(NW % 2 == 0, "8-byte pairs");
 #pragma unroll
     for (int i = 0; i < NW; i += 2) {
@@ -676,31 +640,18 @@ __device__ __forceinline__ void fb_window(const float* row, int l0, float (&win)
         win[i] = __uint_as_float((uint32_t)p);
         win[i + 1] = __uint_as_float((uint32_t)(p >> 32));
     }
-#else
-#pragma unroll
-    for (int i = 0; i < NW; ++i) win[i] = row[fb_slot(min(l0 + i, kFbStrip - 1))];
-#endif
 }
 
 // horizontal window + 2x2 solve of one batch row: thread task -> (row r, TK
 // consecutive output columns starting at strip offset o0).  Box sums restart at
 // every strip offset divisible by 4 (image columns divisible by 4) and slide
 // from there, whatever TK is, so the sums do not depend on the task split.
-#ifndef TBDK_FB_TK
-#define TBDK_FB_TK 2  // output columns per horizontal task (2: twice the threads in the solve phase)
-#endif
-constexpr int kFbTK = TBDK_FB_TK;
-// 1 (tuning builds): 4-column horizontal tasks in half-waves, outputs handed
-// to the other half by v_permlane32_swap (requires kFbTK == 2 and the deferred solve)
-#ifndef TBDK_FB_HX
-#define TBDK_FB_HX 0
-#endif
-static_assert(!TBDK_FB_HX || kFbTK == 2, "TBDK_FB_HX takes 2-column solves");
-static_assert(kFbTK == 2 || kFbTK == 4, "tasks of 2 or 4 columns");
-template <int M, bool GAUSS, int TK = kFbTK>
+constexpr int kFbTK = 2;  // output columns per horizontal task
+template <int M, bool GAUSS>
 __device__ __forceinline__ void fb_hsums(const FbIterArgs& a, const float (*vb)[5][kFbSlots], int r, int o0,
-                                         float (&out)[5][TK])
+                                         float (&out)[5][kFbTK])
 {
+    constexpr int TK = kFbTK;
     const int g0 = o0 & ~3, sk = o0 - g0;  // the box sums' group start, slides to o0 (0 or 2)
 #pragma unroll
     for (int ch = 0; ch < 5; ++ch) {
@@ -731,7 +682,7 @@ __device__ __forceinline__ void fb_hsums(const FbIterArgs& a, const float (*vb)[
 #pragma unroll
             for (int k = 1; k < 4; ++k) v[k] = (v[k - 1] + win[k + 2 * M]) - win[k - 1];
 #pragma unroll
-            for (int k = 0; k < TK; ++k) out[ch][k] = TK == 4 ? v[k] : (sk ? v[2 + k] : v[k]);
+            for (int k = 0; k < TK; ++k) out[ch][k] = sk ? v[2 + k] : v[k];
         }
     }
 }
@@ -779,15 +730,6 @@ __device__ __forceinline__ void fb_solve(const FbIterArgs& a, const float (&out)
     }
 }
 
-template <int M, bool GAUSS>
-__device__ __forceinline__ void fb_horizontal(const FbIterArgs& a, const float (*vb)[5][kFbSlots], int r, int o0,
-                                              int y, int ox0)
-{
-    float out[5][kFbTK];
-    fb_hsums<M, GAUSS>(a, vb, r, o0, out);
-    fb_solve<M, GAUSS>(a, out, o0, y, ox0, true);
-}
-
 // workgroup barrier that waits only for LDS traffic
 __device__ __forceinline__ void fb_lds_barrier()
 {
@@ -795,10 +737,7 @@ __device__ __forceinline__ void fb_lds_barrier()
     __builtin_amdgcn_s_barrier();
 }
 
-#ifndef TBDK_FB_RB
-#define TBDK_FB_RB 4
-#endif
-constexpr int kFbRB = TBDK_FB_RB;  // output rows per batch of fb_iter (4 or 8)
+constexpr int kFbRB = 4;        // output rows per batch of fb_iter
 constexpr int kFbThreads = 256; // two threads per strip column
 
 // M of NR rows t0 + half, t0 + half + 2, ... (relative to the segment's first
@@ -859,7 +798,7 @@ __global__ __launch_bounds__(kFbThreads, (kFbRB == 8 ? (M <= 6 && !GAUSS ? 2 : 1
 {
     constexpr int K = 2 * M + 1;
     constexpr int OW = fb_ow(M);
-    [[maybe_unused]] constexpr int NQ = (OW + kFbTK - 1) / kFbTK;  // horizontal tasks per row
+    constexpr int NQ = (OW + kFbTK - 1) / kFbTK;  // horizontal tasks per row
     constexpr int RR = kFbRB + 2 * M;     // M ring rows
     constexpr int VC = 4;                 // centres per thread in the vertical pass
     __shared__ float mr[5 * RR * kFbStrip];
@@ -889,20 +828,16 @@ __global__ __launch_bounds__(kFbThreads, (kFbRB == 8 ? (M <= 6 && !GAUSS ? 2 : 1
     FbRowB B[NR];
     fb_rows_a<NR>(a, rs, x, ybase, 2 * M, half, A);
     fb_rows_b<NR>(a, rs, x, ybase, 2 * M, half, A, B);
-#if TBDK_FB_DEFER
     // the solve of batch s0's horizontal task runs at the top of the next
     // iteration, in one basic block with the next M rows' finish (independent
     // work the scheduler interleaves with the double-precision chain)
-    static_assert(kFbRB * ((OW + kFbTK - 1) / kFbTK) <= kFbThreads, "one horizontal task per thread and batch (TBDK_FB_RB=8 builds: TBDK_FB_DEFER=0)");
+    static_assert(kFbRB * ((OW + kFbTK - 1) / kFbTK) <= kFbThreads, "one horizontal task per thread and batch");
     float pend[5][kFbTK];
     int pend_o0 = 0, pend_y = 0;
     bool pend_ok = false;
-#endif
     for (int s0 = 0; s0 < nrows; s0 += kFbRB) {
         fb_rows_finish<NR>(a, mr, RR, x, col, ybase, 2 * M + s0, half, A, B);
-#if TBDK_FB_DEFER
         fb_solve<M, GAUSS>(a, pend, pend_o0, pend_y, ox0, pend_ok);
-#endif
         const bool more = s0 + kFbRB < nrows;
         if (more) fb_rows_a<NR>(a, rs, x, ybase, 2 * M + s0 + kFbRB, half, A);
         fb_lds_barrier();
@@ -944,32 +879,6 @@ __global__ __launch_bounds__(kFbThreads, (kFbRB == 8 ? (M <= 6 && !GAUSS ? 2 : 1
         if (more) fb_rows_b<NR>(a, rs, x, ybase, 2 * M + s0 + kFbRB, half, A, B);
         fb_lds_barrier();
         const int nb = min(kFbRB, nrows - s0);
-#if TBDK_FB_DEFER && TBDK_FB_HX
-        {
-            // tasks of 4 columns in lanes 0-31 of each wave (half the LDS reads of
-            // two 2-column tasks); v_permlane32_swap hands outputs 2-3 to lanes
-            // 32-63, so every lane still solves 2 (bit-identical sums: the box
-            // sums restart at the same columns)
-            constexpr int NQ4 = (OW + 3) / 4;
-            const int lane = tid & 63, task = (tid >> 6) * 32 + (lane & 31);
-            const bool in = task < nb * NQ4;
-            const int r = in ? task / NQ4 : 0, q = in ? task - r * NQ4 : 0;
-            float o4[5][4];
-            if (lane < 32) fb_hsums<M, GAUSS, 4>(a, vb, r, 4 * q, o4);
-#pragma unroll
-            for (int ch = 0; ch < 5; ++ch) {
-                const auto p2 = __builtin_amdgcn_permlane32_swap(__builtin_bit_cast(unsigned, o4[ch][0]),
-                                                                 __builtin_bit_cast(unsigned, o4[ch][2]), false, false);
-                const auto p3 = __builtin_amdgcn_permlane32_swap(__builtin_bit_cast(unsigned, o4[ch][1]),
-                                                                 __builtin_bit_cast(unsigned, o4[ch][3]), false, false);
-                pend[ch][0] = lane < 32 ? o4[ch][0] : __builtin_bit_cast(float, p2[0]);
-                pend[ch][1] = lane < 32 ? o4[ch][1] : __builtin_bit_cast(float, p3[0]);
-            }
-            pend_o0 = 4 * q + (lane < 32 ? 0 : 2);
-            pend_ok = in && ox0 + pend_o0 < a.w;
-            pend_y = y0 + s0 + r;
-        }
-#elif TBDK_FB_DEFER
         {
             const bool in = tid < nb * NQ;
             const int r = in ? tid / NQ : 0, q = in ? tid - r * NQ : 0;
@@ -978,20 +887,12 @@ __global__ __launch_bounds__(kFbThreads, (kFbRB == 8 ? (M <= 6 && !GAUSS ? 2 : 1
             pend_y = y0 + s0 + r;
             fb_hsums<M, GAUSS>(a, vb, r, pend_o0, pend);
         }
-#else
-        for (int task = tid; task < nb * NQ; task += kFbThreads) {
-            const int r = task / NQ, q = task - r * NQ;
-            if (ox0 + kFbTK * q < a.w) fb_horizontal<M, GAUSS>(a, vb, r, kFbTK * q, y0 + s0 + r, ox0);
-        }
-#endif
         // the next batch's M rows overwrite ring rows the vertical pass read,
         // and its vertical pass vb rows this horizontal pass reads: both are
         // ordered by the two barriers above (this pass ends before the next
         // batch's first barrier)
     }
-#if TBDK_FB_DEFER
     fb_solve<M, GAUSS>(a, pend, pend_o0, pend_y, ox0, pend_ok);
-#endif
 }
 
 template <int M>

@@ -179,27 +179,6 @@ __device__ __forceinline__ bool any_lane(bool p) { return __builtin_amdgcn_ballo
 #define TBDK_LK_IPACK_FLY 0  // Scharr-on-the-fly instance
 #endif
 
-#ifndef TBDK_LK_MULTI_WAVES
-#define TBDK_LK_MULTI_WAVES 1
-#endif
-// The interpolated (Ix, Iy) row pairs of the level (constant through its Newton
-// steps) kept in LDS instead of VGPRs (1): the level setup writes them once, each
-// step reads them back (one ds_read_b64 per row pair), so the kernel's register
-// peak drops by 2 * NP VGPRs and more waves fit per SIMD (tuning builds: 0 keeps
-// them in VGPRs)
-#ifndef TBDK_LK_GLDS
-#define TBDK_LK_GLDS 0
-#endif
-// A launch ends with its slowest wave: the few points that run to 30 Newton
-// steps on a level (and the waves that carry them) finish long after the
-// rest.  A wave that has taken more than TBDK_LK_PRIO_STEPS steps raises its
-// issue priority (s_setprio), so on a shared SIMD its instructions go first and
-// the straggler runs near its lone-wave speed (0: off)
-#ifndef TBDK_LK_PRIO_STEPS
-#define TBDK_LK_PRIO_STEPS 0
-#endif
-constexpr int kMultiWaves = TBDK_LK_MULTI_WAVES;
-
 // Probe builds (-DTBDK_LK_TRACE, tools/probe_lk_trace.py): every wave writes
 // one record of sixteen u64 (at its launch's base + its wave index, no atomics:
 // a device-wide atomic counter serialises the waves' exits) to a device buffer
@@ -218,12 +197,6 @@ constexpr int kMultiWaves = TBDK_LK_MULTI_WAVES;
 __device__ unsigned long long* g_lk_trace;
 __device__ unsigned int g_lk_trace_cap;
 static unsigned g_lk_trace_next;  // host: records handed out so far
-#endif
-
-#ifdef TBDK_LK_MULTI_MINW  // waves per SIMD the register allocation must allow (tuning builds)
-#define TBDK_MULTI_BOUNDS __launch_bounds__(64 * TBDK_LK_MULTI_WAVES, TBDK_LK_MULTI_MINW)
-#else
-#define TBDK_MULTI_BOUNDS __launch_bounds__(64 * TBDK_LK_MULTI_WAVES)
 #endif
 
 // FLY: the Scharr derivatives of the window are computed from the u8 level in
@@ -252,7 +225,7 @@ static unsigned g_lk_trace_next;  // host: records handed out so far
 // while the included text leaves every forward instance's instructions as they
 // were (compared by disassembly).
 template <int WW, int WH, bool FLY, bool DENSE = false>
-__global__ TBDK_MULTI_BOUNDS void lk_multi_kernel(LkArgs a)
+__global__ __launch_bounds__(64) void lk_multi_kernel(LkArgs a)
 {
     constexpr bool BACK = false;
     const LkBack bk{};
@@ -262,7 +235,7 @@ __global__ TBDK_MULTI_BOUNDS void lk_multi_kernel(LkArgs a)
 // the backward pass of the forward-backward check: a kernel of its own name,
 // Scharr on the fly
 template <int WW, int WH>
-__global__ TBDK_MULTI_BOUNDS void lk_multi_back_kernel(LkArgs a, LkBack bk)
+__global__ __launch_bounds__(64) void lk_multi_back_kernel(LkArgs a, LkBack bk)
 {
     constexpr bool BACK = true, FLY = true, DENSE = false;
 #include "klt_lk_multi_body.inc"
@@ -286,12 +259,12 @@ bool lk_multi_supported(int win_w, int win_h)
 hipError_t launch_lk_multi(const LkArgs& a, bool fly, hipStream_t s)
 {
     if (!lk_multi_supported(a.win_w, a.win_h)) return hipErrorNotSupported;
-    const int per_wg = kMultiWaves * (64 / a.win_w);  // waves of P points
-    const dim3 grid((a.n + per_wg - 1) / per_wg), block(64 * kMultiWaves);
+    const int per_wg = 64 / a.win_w;  // one wave of P points
+    const dim3 grid((a.n + per_wg - 1) / per_wg), block(64);
 #ifdef TBDK_LK_TRACE
     LkArgs at = a;
     at.trace_base = g_lk_trace_next;
-    g_lk_trace_next += grid.x * kMultiWaves;
+    g_lk_trace_next += grid.x;
     const LkArgs& la = at;
 #else
     const LkArgs& la = a;
@@ -313,12 +286,12 @@ hipError_t launch_lk_multi(const LkArgs& a, bool fly, hipStream_t s)
 hipError_t launch_lk_multi_back(const LkArgs& a, const LkBack& b, hipStream_t s)
 {
     if (!lk_multi_supported(a.win_w, a.win_h)) return hipErrorNotSupported;
-    const int per_wg = kMultiWaves * (64 / a.win_w);  // waves of P points
-    const dim3 grid((a.n + per_wg - 1) / per_wg), block(64 * kMultiWaves);
+    const int per_wg = 64 / a.win_w;  // one wave of P points
+    const dim3 grid((a.n + per_wg - 1) / per_wg), block(64);
 #ifdef TBDK_LK_TRACE
     LkArgs at = a;
     at.trace_base = g_lk_trace_next;
-    g_lk_trace_next += grid.x * kMultiWaves;
+    g_lk_trace_next += grid.x;
     const LkArgs& la = at;
 #else
     const LkArgs& la = a;
@@ -339,8 +312,8 @@ hipError_t launch_lk_multi_back(const LkArgs& a, const LkBack& b, hipStream_t s)
 hipError_t launch_lk_multi_dense(const LkArgs& a, hipStream_t s)
 {
     if (!lk_multi_supported(a.win_w, a.win_h)) return hipErrorNotSupported;
-    const int per_wg = kMultiWaves * (64 / a.win_w);  // waves of P points
-    const dim3 grid((a.n + per_wg - 1) / per_wg), block(64 * kMultiWaves);
+    const int per_wg = 64 / a.win_w;  // one wave of P points
+    const dim3 grid((a.n + per_wg - 1) / per_wg), block(64);
     switch (a.win_w) {
 #define TBDK_CASE(W)                                                                          \
     case W:                                                                                   \

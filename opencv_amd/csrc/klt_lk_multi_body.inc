@@ -8,17 +8,16 @@
     constexpr int NP = (WH + 1) / 2;   // packed row pairs (rows 2q, 2q+1)
     constexpr int IM = FLY ? TBDK_LK_IPACK_FLY : TBDK_LK_IPACK;
     constexpr bool IPACK = IM == 1, ILIN = IM == 2;
-    constexpr bool GL = TBDK_LK_GLDS != 0;
-    constexpr bool kSoloOk = P >= 2 && !GL && !ILIN;  // one-point steps (LkArgs::solo_min)
-    // GL: this wave's (Ix, Iy) row pairs, [row pair][lane] (8 B per lane: b64 accesses)
-    __shared__ uint2 sg[GL ? NP * kMultiWaves : 1][64];
+    constexpr bool kSoloOk = P >= 2 && !ILIN;  // one-point steps (LkArgs::solo_min)
     const int lane = threadIdx.x & 63;
-    uint2(*const sgw)[64] = &sg[GL ? (threadIdx.x >> 6) * NP : 0];
     // point k of the wave owns lanes [1 + k*WW, 1 + (k+1)*WW); lane 0 (and any
     // lane past the last point) is idle with k == P and contributes 0
     const int k = lane == 0 ? P : (lane - 1) / WW;
     const int x = k < P ? lane - 1 - k * WW : 0;
-    const int wave = xcd_swizzle(blockIdx.x, gridDim.x) * kMultiWaves + (threadIdx.x >> 6);
+    // the wave's index in the launch: one wave per workgroup, so the second term
+    // is 0 (written out: it keeps the kernels' instructions exactly as compared
+    // by disassembly, DESIGN.md)
+    const int wave = xcd_swizzle(blockIdx.x, gridDim.x) + (threadIdx.x >> 6);
     // the point's index in a segmented list (seg_point) and its coordinates: the
     // segment's count and the point are loaded together, the point speculatively
     // (index s * stride + j lies inside segment s's stride-sized row of the
@@ -124,9 +123,6 @@
         outy = a.next_pts[2 * i + 1];
     }
     int status = 1, nit = 0;
-#if TBDK_LK_PRIO_STEPS > 0
-    int wsteps = 0;  // Newton steps this wave has run (wave-uniform)
-#endif
 #if defined(TBDK_LK_PROBE_RELOADS) && TBDK_LK_PROBE_RELOADS == 2
     int nrl = 0;
 #endif
@@ -234,7 +230,6 @@
                 const int y1 = two ? bilin_s<0>(dy1, dy2, dw2, dw3, rnd14) : 0;
                 gxk[q] = pack_shr<W_BITS1>(x0, x1);
                 gyk[q] = pack_shr<W_BITS1>(y0, y1);
-                if constexpr (GL) sgw[q][lane] = make_uint2(gxk[q], gyk[q]);
                 if constexpr (ILIN) {
                     cgx = sdot2(ipq, gxk[q], cgx);
                     cgy = sdot2(ipq, gyk[q], cgy);
@@ -562,9 +557,6 @@
 #ifdef TBDK_LK_TRACE
             ++tr_steps;
 #endif
-#if TBDK_LK_PRIO_STEPS > 0
-            if (++wsteps == TBDK_LK_PRIO_STEPS) __builtin_amdgcn_s_setprio(3);
-#endif
             if constexpr (kSoloOk) {
                 // one point left stepping (LkArgs::solo_min): its remaining steps
                 // on all the wave's lanes, the window rows split over the P lane
@@ -605,7 +597,6 @@
             }
             bilinear_weights(nextx - inx, nexty - iny, w0, w1);
             int b[2] = {0, 0};
-            if constexpr (GL) asm volatile("" ::: "memory");  // the (Ix, Iy) pairs are re-read from LDS every step
 #pragma unroll
             for (int q = 0; q < NP; ++q) {
                 const int r = 2 * q;
@@ -627,12 +618,7 @@
                                                bilin_c(jp[r + 1], jp[r + 2], w0, w1, ic[r + 1]))
                                    : pack_diff(bilin_c(jp[r], jp[r + 1], w0, w1, ic[r]), 0);
                 }
-                uint32_t gx = gxk[q], gy = gyk[q];
-                if constexpr (GL) {
-                    const uint2 g = sgw[q][lane];
-                    gx = g.x;
-                    gy = g.y;
-                }
+                const uint32_t gx = gxk[q], gy = gyk[q];
                 b[0] = sdot2(d, gx, b[0]);
                 b[1] = sdot2(d, gy, b[1]);
 #ifdef TBDK_LK_NEWTON_SB

@@ -190,15 +190,6 @@ int tbdk_ctx_set_option(tbdk_ctx* ctx, const char* name, int64_t value)
         ctx->opt_tbd_early_la = value;
         return TBDK_OK;
     }
-    if (std::strcmp(name, "tbd_early_prio") == 0) {
-        ctx->opt_tbd_early_prio = value != 0;
-        return TBDK_OK;
-    }
-    if (std::strcmp(name, "tbd_early_order") == 0) {
-        if (value < 0 || value > 2) return TBDK_EINVAL;
-        ctx->opt_tbd_early_order = (int)value;
-        return TBDK_OK;
-    }
     if (std::strcmp(name, "fb_prep_ahead") == 0) {
         ctx->opt_fb_prep_ahead = value != 0;
         return TBDK_OK;
@@ -248,20 +239,12 @@ int tbdk_ctx_set_option(tbdk_ctx* ctx, const char* name, int64_t value)
         ctx->opt_tbd_fit_gate = value != 0;
         return TBDK_OK;
     }
-    if (std::strcmp(name, "tbd_la_defer") == 0) {
-        ctx->opt_tbd_la_defer = value != 0;
-        return TBDK_OK;
-    }
     if (std::strcmp(name, "gftt_compact") == 0) {
         ctx->opt_gftt_compact = value != 0;
         return TBDK_OK;
     }
     if (std::strcmp(name, "tbd_borrow_l0") == 0) {
         ctx->opt_tbd_borrow_l0 = value != 0;
-        return TBDK_OK;
-    }
-    if (std::strcmp(name, "tbd_async_la") == 0) {
-        ctx->opt_tbd_async_la = value != 0;
         return TBDK_OK;
     }
     if (std::strcmp(name, "gftt_inline") == 0) {
@@ -273,7 +256,7 @@ int tbdk_ctx_set_option(tbdk_ctx* ctx, const char* name, int64_t value)
         return TBDK_OK;
     }
     if (std::strcmp(name, "pyr_fuse") == 0) {
-        if (value < 0 || value > 2) return TBDK_EINVAL;
+        if (value < 0 || value > 1) return TBDK_EINVAL;
         ctx->opt_pyr_fuse = (int)value;
         return TBDK_OK;
     }
@@ -296,11 +279,6 @@ int tbdk_ctx_set_option(tbdk_ctx* ctx, const char* name, int64_t value)
     }
     if (std::strcmp(name, "lk_seg_inline") == 0) {
         ctx->opt_lk_seg_inline = value != 0;
-        return TBDK_OK;
-    }
-    if (std::strcmp(name, "tbd_ahead_at") == 0) {
-        if (value < 0 || value > 2) return TBDK_EINVAL;
-        ctx->opt_tbd_ahead_at = (int)value;
         return TBDK_OK;
     }
     if (std::strcmp(name, "tbd_gftt_ahead") == 0) {

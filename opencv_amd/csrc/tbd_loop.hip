@@ -27,16 +27,12 @@
 #include <sched.h>
 
 #include <algorithm>
-#include <atomic>
 #include <chrono>
-#include <condition_variable>
 #include <cmath>
 #include <cstdlib>
 #include <cstring>
-#include <functional>
 #include <new>
 #include <queue>
-#include <thread>
 #include <vector>
 
 #include "box_fit.hpp"
@@ -228,98 +224,12 @@ __global__ __launch_bounds__(64 * kFitWaves) void tbd_fit_kernel(const FitEntry*
     }
 }
 
-// The loop's launch worker (ctx option tbd_async_la): a host thread that issues
-// the look-ahead PyrLK launches (the speculative one after the fit sync, the
-// post-tracker one at the end of the step) while the loop's own thread goes on
-// with the tracker step and the next frame.  Those launches feed no result back
-// to the host within the step, so each is a job handed over in FIFO order; the
-// loop drains the queue (waits for every posted job) before any host call that
-// depends on what a job enqueued: a wait on la_done, a launch on the look-ahead
-// stream, the end of a public call.  A HIP launch costs 2.4-3.4 us of host time
-//  and the speculative block ~6-14 us, all of it on the frame's
-// host chain between the fit and the next critical PyrLK launch.
-class LaunchWorker {
-public:
-    explicit LaunchWorker(int device) : device_(device), th_([this] { run(); }) {}
-    ~LaunchWorker()
-    {
-        {
-            std::lock_guard<std::mutex> lk(mu_);
-            stop_ = true;
-        }
-        cv_.notify_one();
-        th_.join();
-    }
-    // queue f (runs on the worker, in posting order)
-    void post(std::function<int()> f)
-    {
-        while (head_.load(std::memory_order_relaxed) - tail_.load(std::memory_order_acquire) >= kJobs)
-            __builtin_ia32_pause();
-        jobs_[head_.load(std::memory_order_relaxed) % kJobs] = std::move(f);
-        head_.fetch_add(1, std::memory_order_seq_cst);  // seq_cst pair with run()'s sleeping_ / head_
-        if (sleeping_.load(std::memory_order_seq_cst)) {
-            std::lock_guard<std::mutex> lk(mu_);
-            cv_.notify_one();
-        }
-    }
-    // wait until every posted job has run; the first error since the last drain
-    int drain()
-    {
-        while (tail_.load(std::memory_order_acquire) != head_.load(std::memory_order_relaxed)) __builtin_ia32_pause();
-        return err_.exchange(TBDK_OK);
-    }
-
-private:
-    static constexpr unsigned kJobs = 8;
-    static constexpr double kSpinUs = 1000.0;  // spin this long for the next job, then sleep
-    void run()
-    {
-        (void)hipSetDevice(device_);
-        using clk = std::chrono::steady_clock;
-        auto idle0 = clk::now();
-        for (;;) {
-            const unsigned tl = tail_.load(std::memory_order_relaxed);
-            if (head_.load(std::memory_order_acquire) != tl) {
-                const int r = jobs_[tl % kJobs]();
-                jobs_[tl % kJobs] = nullptr;
-                if (r != TBDK_OK) {
-                    int ok = TBDK_OK;
-                    err_.compare_exchange_strong(ok, r);
-                }
-                tail_.store(tl + 1, std::memory_order_release);
-                idle0 = clk::now();
-                continue;
-            }
-            if (std::chrono::duration<double, std::micro>(clk::now() - idle0).count() < kSpinUs) {
-                for (int p = 0; p < 16; ++p) __builtin_ia32_pause();
-                continue;
-            }
-            std::unique_lock<std::mutex> lk(mu_);
-            sleeping_.store(true, std::memory_order_seq_cst);
-            cv_.wait(lk, [&] { return stop_ || head_.load(std::memory_order_seq_cst) != tail_.load(std::memory_order_relaxed); });
-            sleeping_.store(false, std::memory_order_relaxed);
-            if (stop_ && head_.load(std::memory_order_acquire) == tail_.load(std::memory_order_relaxed)) return;
-            idle0 = clk::now();
-        }
-    }
-    int device_;
-    std::function<int()> jobs_[kJobs];
-    std::atomic<unsigned> head_{0}, tail_{0};
-    std::atomic<int> err_{TBDK_OK};
-    std::atomic<bool> sleeping_{false};
-    std::mutex mu_;
-    std::condition_variable cv_;
-    bool stop_ = false;
-    std::thread th_;  // last: started once the members above exist
-};
-
 }  // namespace tbdk
 
 using namespace tbdk;
 
 struct tbdk_tbd {
     tbdk_ctx* ctx = nullptr;
-    LaunchWorker* worker = nullptr;  // ctx option tbd_async_la (read by tbdk_tbd_create)
     tbdk_tbd_config cfg;
     // three pyramids in rotation: this frame's (cur), the previous frame's and
     // the look-ahead frame's, so the look-ahead build never overwrites a
@@ -391,8 +301,6 @@ struct tbdk_tbd {
     hipStream_t la_stream = nullptr;
     bool la_pyr = false;             // pyr[cur] already holds la_frame's pyramid
     bool la_lk = false;              // ... and the la_member slots are tracked into it
-    int la_defer_n = 0;              // look-ahead PyrLK left to the next step (h_la's first la_defer_n slots)
-    bool la_defer_eig = false;       // ... behind the post-tracker GFTT's eigenvalue kernel
     // pinned host staging (reuse rules: see tbdk_tbd_step)
     // [fit entries: S FitEntry][LK slot lists: S int32 (unchanged sets, then refreshed ones)]
     void* h_pre = nullptr;
@@ -497,18 +405,6 @@ inline uint64_t box_key(int x, int y, int w, int h)
            (uint64_t)(uint16_t)h;
 }
 
-// the launch worker's queue drained (a no-op without the worker): the first
-// error of a posted job, else TBDK_OK
-inline int drain(tbdk_tbd* t) { return t->worker ? t->worker->drain() : TBDK_OK; }
-
-// run f now, or (launch worker) post it
-inline int run_or_post(tbdk_tbd* t, std::function<int()> f)
-{
-    if (!t->worker) return f();
-    t->worker->post(std::move(f));
-    return TBDK_OK;
-}
-
 // Every PyrLK launch of the loop: n launch indices over the segment list
 // (d_list on the device, h_list its host copy), pyramid A -> B on stream s.
 // With ctx option tbd_fb_check the backward pass (B -> A over the same list)
@@ -571,11 +467,6 @@ int end_borrow(tbdk_tbd* t, hipStream_t s)
 int release(tbdk_tbd* t)
 {
     if (!t) return TBDK_OK;
-    if (t->worker) {  // every posted launch issued before the streams are synchronised
-        (void)t->worker->drain();
-        delete t->worker;
-        t->worker = nullptr;
-    }
     if (t->side) (void)hipStreamSynchronize(t->side);
     if (t->post_done) (void)hipEventDestroy(t->post_done);
     if (t->fit_done) (void)hipEventDestroy(t->fit_done);
@@ -780,15 +671,10 @@ int tbdk_tbd_create(tbdk_ctx* ctx, const tbdk_tbd_config* cfg, tbdk_tbd** out)
     else if (e == hipSuccess && (e = hipStreamCreateWithPriority(&t->la_s, hipStreamNonBlocking, prio_least)) == hipSuccess)
         t->own_la = true;
     if (e == hipSuccess) e = hipEventCreateWithFlags(&t->eig_done, hipEventDisableTiming);
-    // the early GFTT at the lowest priority (ctx option tbd_early_prio, read here:
-    // 1 = the highest, for launch orders that put it behind the critical PyrLK)
-    if (e == hipSuccess && ctx->tbd_early && !ctx->opt_tbd_early_prio) {
-        t->early_s = ctx->tbd_early;
-    } else if (e == hipSuccess) {
-        e = hipStreamCreateWithPriority(&t->early_s, hipStreamNonBlocking,
-                                        ctx->opt_tbd_early_prio ? prio_greatest : prio_least);
-        if (e == hipSuccess) t->own_early = true;
-    }
+    // the early GFTT at the lowest priority
+    if (e == hipSuccess && ctx->tbd_early) t->early_s = ctx->tbd_early;
+    else if (e == hipSuccess && (e = hipStreamCreateWithPriority(&t->early_s, hipStreamNonBlocking, prio_least)) == hipSuccess)
+        t->own_early = true;
     for (hipEvent_t& ev : t->early_done)
         if (e == hipSuccess) e = hipEventCreateWithFlags(&ev, hipEventDisableTiming);
     if (e == hipSuccess) e = hipEventCreateWithFlags(&t->ahead_tail, hipEventDisableTiming);
@@ -818,13 +704,6 @@ int tbdk_tbd_create(tbdk_ctx* ctx, const tbdk_tbd_config* cfg, tbdk_tbd** out)
     t->npts_of = FlatMap<unsigned>(4 * (size_t)cfg->max_tracks);
     t->erow_of = FlatMap<uint64_t>(4 * (size_t)cfg->max_tracks);
     t->ahead_row_of = FlatMap<uint64_t>(4 * (size_t)cfg->max_tracks);
-    if (ctx->opt_tbd_async_la) {
-        t->worker = new (std::nothrow) LaunchWorker(ctx->device);
-        if (!t->worker) {
-            release(t);
-            return TBDK_ENOMEM;
-        }
-    }
     rc = gftt_reserve(t->gftt, ctx->device, cfg->max_tracks, (int64_t)cfg->width * cfg->height * 2);
     if (rc == TBDK_OK) rc = gftt_reserve(t->gftt2, ctx->device, cfg->max_tracks, (int64_t)cfg->width * cfg->height * 2);
     if (rc != TBDK_OK) {
@@ -884,6 +763,161 @@ long g_sub_n = 0;
 #define SUB_MARK(k) ((void)0)
 #endif
 
+// One early GFTT ROI: the box (x, y, w, h) if it lies beyond the tracker's
+// bounds filter (or `any`), clipped to the frame, at least 3x3 and not yet in
+// row_of, is appended to rois and row_of maps it to its index there
+void gather_roi(const tbdk_tbd_config& c, int x, int y, int w, int h, bool any, FlatMap<uint64_t>& row_of,
+                std::vector<tbdk_roi>& rois)
+{
+    const bool beyond = x >= c.bounds_xmax || y >= c.bounds_ymax || x + w < c.bounds_xmin || y + h < c.bounds_ymin;
+    if (!any && !beyond) return;
+    const int x0 = std::max(x, 0), y0 = std::max(y, 0);
+    const int x1 = std::min(x + w, c.width), y1 = std::min(y + h, c.height);
+    if (x1 - x0 < 3 || y1 - y0 < 3) return;
+    if (!row_of.insert(box_key(x0, y0, x1 - x0, y1 - y0), (int)rois.size())) return;
+    rois.push_back(tbdk_roi{x0, y0, x1 - x0, y1 - y0});
+}
+
+// one launch of the early GFTT over rois[0, n) into row set `set` from row
+// `tab0` on, over the image at img (the pinned table at h_etab[set] + tab0)
+int early_launch(tbdk_tbd* t, const tbdk_gftt_params& gp, const tbdk_roi* rois, int n, int set, int tab0,
+                 const uint8_t* img, int ipitch)
+{
+    const tbdk_tbd_config& c = t->cfg;
+    GfttPlan eplan;
+    GfttRoi* htab = t->h_etab[set] + tab0;
+    int rc = gftt_prepare(rois, n, c.width, c.height, &gp, htab, &eplan);
+    if (rc != TBDK_OK) return rc;
+    hipStream_t es = t->early_s;  // ordered at the top of the step
+    const GfttRoi* dtab = t->zc ? t->d_etab + (htab - t->h_etab[0]) : t->d_etab;
+    if (!t->zc) {
+        hipError_t e = hipMemcpyAsync(t->d_etab, htab, sizeof(GfttRoi) * n, hipMemcpyHostToDevice, es);
+        if (e != hipSuccess) return map_status(e);
+    }
+    const int row0 = c.max_tracks * (1 + set) + tab0;
+    rc = gftt_launch(t->ctx, t->gftt, img, ipitch, dtab, eplan, &gp,
+                     reinterpret_cast<float*>(t->slot_pts + (size_t)row0 * kSlotPts), t->slot_counts + row0, es,
+                     nullptr, kSlotPts, htab);
+    if (rc != TBDK_OK) return rc;
+    return map_status(hipEventRecord(t->early_done[set], es));
+}
+
+// The early GFTT over the detections that will start new tracks: every
+// detection before the first tracks exist, else those beyond the tracker's
+// bounds filter (a track on them is predicted there and deleted before the
+// assignment).  On the low-priority `early_s`, launched first in the step
+// (it is needed only after the tracker step, and overlaps this step's
+// PyrLK and fit); the post-tracker phase takes its corners for every
+// refreshed set whose box equals one of these ROIs.  t->erois starts with
+// the ROIs an ahead launch covered; the rest are launched here over this
+// frame's pyramid P, and *launched is set when there are any.
+int launch_early_gftt(tbdk_tbd* t, const tbdk_gftt_params& gp, const tbdk_pyr& P, int frame_id,
+                      const tbdk_detection* dets, int ndets, bool* launched)
+{
+    const tbdk_tbd_config& c = t->cfg;
+    const size_t n0 = t->erois.size();  // taken over from the ahead launch
+    const bool all_new = t->tracker->getTracks().empty();
+    for (int i = 0; i < ndets && (int)t->erois.size() < c.max_tracks; ++i)
+        gather_roi(c, dets[i].x, dets[i].y, dets[i].width, dets[i].height, all_new, t->erow_of, t->erois);
+    // re-detection frames: every existing track's set is refreshed in its box
+    // after updateAssignedTracks (tbd.cpp:948-965), which depends only on the
+    // assigned detection and the track's box history; speculate the detection
+    // of largest overlap with the track's last box and GFTT that box early
+    // (a track assigned otherwise, or not at all, takes the post-tracker GFTT)
+    if (t->ctx->opt_tbd_early_gftt >= 2 && !all_new && frame_id % c.redetect_every == 0 && ndets > 0) {
+        auto& order = t->det_order;
+        order.resize((size_t)ndets);
+        int maxw = 0;
+        for (int i = 0; i < ndets; ++i) {
+            order[(size_t)i] = i;
+            maxw = std::max(maxw, dets[i].width);
+        }
+        std::sort(order.begin(), order.end(), [&](int a, int b) { return dets[a].x < dets[b].x; });
+        for (const auto& tr : t->tracker->getTracks()) {
+            if ((int)t->erois.size() >= c.max_tracks) break;
+            if (!t->slot_of.find(tr.id)) continue;
+            const tbd::Rect& lb = tr.bboxes.back();
+            if (lb.x >= c.bounds_xmax || lb.y >= c.bounds_ymax) continue;  // deleted by the bounds filter
+            auto lo = std::lower_bound(order.begin(), order.end(), lb.x - maxw,
+                                       [&](int a, int x) { return dets[a].x < x; });
+            int best = -1;
+            double bo = 0.0;
+            for (auto it = lo; it != order.end() && dets[*it].x <= lb.x + lb.width; ++it) {
+                const tbdk_detection& d = dets[*it];
+                const double o = tbd::computeBoundingBoxOverlap(lb, tbd::Rect(d.x, d.y, d.width, d.height));
+                if (o > bo) {
+                    bo = o;
+                    best = *it;
+                }
+            }
+            if (best < 0) continue;
+            const tbdk_detection& d = dets[best];
+            const unsigned nprior = tr.historyLength < 4 ? (unsigned)tr.historyLength : 4u;
+            unsigned wsum = 0, hsum = 0;
+            for (unsigned k = tr.bboxes.size() - nprior; k < tr.bboxes.size(); ++k) {
+                wsum += tr.bboxes[k].width;
+                hsum += tr.bboxes[k].height;
+            }
+            const int w = (int)((wsum + d.width) / (nprior + 1)), h = (int)((hsum + d.height) / (nprior + 1));
+            const tbd::Rect r = tbd::rect_from_point2d((double)d.x + (d.width / 2 - w / 2),
+                                                       (double)d.y + (d.height / 2 - h / 2), w, h);
+            gather_roi(c, r.x, r.y, r.width, r.height, true, t->erow_of, t->erois);
+        }
+    }
+    if (t->erois.size() > n0) {  // the ROIs no ahead launch covered
+        const tbdk_level& L0 = P.lv[0];
+        const int rc = early_launch(t, gp, t->erois.data() + n0, (int)(t->erois.size() - n0), t->eb, (int)n0,
+                                    L0.data + (size_t)L0.pad * L0.pitch + L0.pad, L0.pitch);
+        if (rc != TBDK_OK) return rc;
+        *launched = true;
+    }
+    return TBDK_OK;
+}
+
+// the next frame's new-track ROIs (its detections beyond the bounds filter,
+// as above), launched ahead over the caller's next frame into the next row
+// set, right after this step's early launch: that frame's step takes them
+// over, so its refreshed-set PyrLK no longer waits for a GFTT launched one
+// step before it (tbdk_tbd_run knows the next frame's detections)
+int launch_gftt_ahead(tbdk_tbd* t, const tbdk_gftt_params& gp, int frame_id, const uint8_t* next, int next_pitch,
+                      const tbdk_detection* next_dets, int next_ndets)
+{
+    const tbdk_tbd_config& c = t->cfg;
+    if (!next || !next_dets || next_ndets <= 0 || !t->ctx->opt_tbd_gftt_ahead || t->tracker->getTracks().empty())
+        return TBDK_OK;
+    const int nb = (t->eb + 1) % kEarlySets;
+    t->ahead_rois.clear();
+    t->ahead_row_of.clear();
+    for (int i = 0; i < next_ndets && (int)t->ahead_rois.size() < c.max_tracks; ++i)
+        gather_roi(c, next_dets[i].x, next_dets[i].y, next_dets[i].width, next_dets[i].height, false,
+                   t->ahead_row_of, t->ahead_rois);
+    if (t->ahead_rois.empty()) return TBDK_OK;
+    const int rc = early_launch(t, gp, t->ahead_rois.data(), (int)t->ahead_rois.size(), nb, 0, next, next_pitch);
+    if (rc != TBDK_OK) return rc;
+    t->ahead_id = frame_id + 1;
+    t->ahead_frame = next;
+    t->ahead_pitch = next_pitch;
+    t->ahead_set = nb;
+    t->ahead_any = true;
+    return TBDK_OK;
+}
+
+// A look-ahead PyrLK launch: the n sets of h_list (d_list its device side),
+// pyramid A -> B, on la_s behind the look-ahead pyramid (la_ready, unless that
+// was built on la_s itself) and behind `after` when given; la_done marks its end
+int launch_la_lk(tbdk_tbd* t, const tbdk_lk_params& lp, const tbdk_pyr* A, const tbdk_pyr* B, int n,
+                 int32_t* d_list, const int32_t* h_list, hipEvent_t after)
+{
+    hipStream_t ls = t->la_s;
+    hipError_t e = t->la_stream == ls ? hipSuccess : wait_if_pending(ls, t->la_ready);
+    if (e == hipSuccess && after) e = wait_if_pending(ls, after);
+    if (e == hipSuccess && !t->zc) e = hipMemcpyAsync(d_list, h_list, sizeof(int32_t) * n, hipMemcpyHostToDevice, ls);
+    if (e != hipSuccess) return map_status(e);
+    const int r = loop_lk(t, A, B, n * kSlotPts, lp, ls, d_list, h_list);
+    if (r != TBDK_OK) return r;
+    return map_status(hipEventRecord(t->la_done, ls));
+}
+
 // One frame.  With next != nullptr the step also enqueues look-ahead work for
 // the next frame: its pyramid behind this frame's fit (the device has it to run
 // while the host tracker runs), and its PyrLK of the unchanged point sets
@@ -916,14 +950,11 @@ int step_impl(tbdk_tbd* t, const uint8_t* frame, int pitch, int frame_id, const 
     const bool had_la_lk = t->la_lk;
     const bool la_lk = la_valid && had_la_lk;
 
-
     if (t->la_pyr && t->la_stream != s) {  // the look-ahead pyramid was built on another stream
         hipError_t e = wait_if_pending(s, t->la_ready);
         if (e != hipSuccess) return map_status(e);
     }
     if (had_la_lk && !la_valid) {  // discarded: it may still read the pyramid about to be rebuilt
-        rc = drain(t);
-        if (rc != TBDK_OK) return rc;
         hipError_t e = wait_if_pending(s, t->la_done);
         if (e != hipSuccess) return map_status(e);
     }
@@ -952,14 +983,6 @@ int step_impl(tbdk_tbd* t, const uint8_t* frame, int pitch, int frame_id, const 
         if (e != hipSuccess) return map_status(e);
     }
 
-    // ---- early GFTT over the detections that will start new tracks: every
-    // detection before the first tracks exist, else those beyond the tracker's
-    // bounds filter (a track on them is predicted there and deleted before the
-    // assignment).  On the low-priority `early_s`, launched first in the step
-    // (it is needed only after the tracker step, and overlaps this step's
-    // PyrLK and fit); the
-    // post-tracker phase takes its corners for every refreshed set whose box
-    // equals one of these ROIs.
     const int S = c.max_tracks;
     const int erow0 = S * (1 + t->eb);  // this step's early GFTT rows (see tbdk_tbd::src_row)
     // the ROIs the previous step launched ahead for this frame (tbd_gftt_ahead):
@@ -979,148 +1002,9 @@ int step_impl(tbdk_tbd* t, const uint8_t* frame, int pitch, int frame_id, const 
     t->ahead_id = INT_MIN;
     t->ahead_set = -1;
     bool early_launched = ahead_in && !t->erois.empty();
-    // one launch of the early GFTT over rois[0, n) into row set `set` from row
-    // `row0` on, over the image at img (the pinned table at h_etab[set] + tab0)
-    auto early_launch = [&](const tbdk_roi* rois, int n, int set, int tab0, const uint8_t* img, int ipitch) -> int {
-        GfttPlan eplan;
-        GfttRoi* htab = t->h_etab[set] + tab0;
-        int rc2 = gftt_prepare(rois, n, c.width, c.height, &gp, htab, &eplan);
-        if (rc2 != TBDK_OK) return rc2;
-        hipStream_t es = t->early_s;  // ordered at the top of the step
-        const GfttRoi* dtab = t->zc ? t->d_etab + (htab - t->h_etab[0]) : t->d_etab;
-        if (!t->zc) {
-            hipError_t e = hipMemcpyAsync(t->d_etab, htab, sizeof(GfttRoi) * n, hipMemcpyHostToDevice, es);
-            if (e != hipSuccess) return map_status(e);
-        }
-        const int row0 = S * (1 + set) + tab0;
-        rc2 = gftt_launch(t->ctx, t->gftt, img, ipitch, dtab, eplan, &gp,
-                          reinterpret_cast<float*>(t->slot_pts + (size_t)row0 * kSlotPts), t->slot_counts + row0, es,
-                          nullptr, kSlotPts, htab);
-        if (rc2 != TBDK_OK) return rc2;
-        return map_status(hipEventRecord(t->early_done[set], es));
-    };
-    auto launch_early_gftt = [&]() -> int {
-        if (!c.use_klt || !t->ctx->opt_tbd_early_gftt) return TBDK_OK;
-        const size_t n0 = t->erois.size();  // taken over from the ahead launch
-        const bool all_new = t->tracker->getTracks().empty();
-        for (int i = 0; i < ndets && (int)t->erois.size() < c.max_tracks; ++i) {
-            const tbdk_detection& d = dets[i];
-            const bool beyond = d.x >= c.bounds_xmax || d.y >= c.bounds_ymax || d.x + d.width < c.bounds_xmin ||
-                                d.y + d.height < c.bounds_ymin;
-            if (!all_new && !beyond) continue;
-            const int x0 = std::max(d.x, 0), y0 = std::max(d.y, 0);
-            const int x1 = std::min(d.x + d.width, c.width), y1 = std::min(d.y + d.height, c.height);
-            if (x1 - x0 < 3 || y1 - y0 < 3) continue;
-            if (!t->erow_of.insert(box_key(x0, y0, x1 - x0, y1 - y0), (int)t->erois.size())) continue;
-            t->erois.push_back(tbdk_roi{x0, y0, x1 - x0, y1 - y0});
-        }
-        // re-detection frames: every existing track's set is refreshed in its box
-        // after updateAssignedTracks (tbd.cpp:948-965), which depends only on the
-        // assigned detection and the track's box history; speculate the detection
-        // of largest overlap with the track's last box and GFTT that box early
-        // (a track assigned otherwise, or not at all, takes the post-tracker GFTT)
-        if (t->ctx->opt_tbd_early_gftt >= 2 && !all_new && frame_id % c.redetect_every == 0 && ndets > 0) {
-            auto& order = t->det_order;
-            order.resize((size_t)ndets);
-            int maxw = 0;
-            for (int i = 0; i < ndets; ++i) {
-                order[(size_t)i] = i;
-                maxw = std::max(maxw, dets[i].width);
-            }
-            std::sort(order.begin(), order.end(), [&](int a, int b) { return dets[a].x < dets[b].x; });
-            for (const auto& tr : t->tracker->getTracks()) {
-                if ((int)t->erois.size() >= c.max_tracks) break;
-                if (!t->slot_of.find(tr.id)) continue;
-                const tbd::Rect& lb = tr.bboxes.back();
-                if (lb.x >= c.bounds_xmax || lb.y >= c.bounds_ymax) continue;  // deleted by the bounds filter
-                auto lo = std::lower_bound(order.begin(), order.end(), lb.x - maxw,
-                                           [&](int a, int x) { return dets[a].x < x; });
-                int best = -1;
-                double bo = 0.0;
-                for (auto it = lo; it != order.end() && dets[*it].x <= lb.x + lb.width; ++it) {
-                    const tbdk_detection& d = dets[*it];
-                    const double o = tbd::computeBoundingBoxOverlap(lb, tbd::Rect(d.x, d.y, d.width, d.height));
-                    if (o > bo) {
-                        bo = o;
-                        best = *it;
-                    }
-                }
-                if (best < 0) continue;
-                const tbdk_detection& d = dets[best];
-                const unsigned nprior = tr.historyLength < 4 ? (unsigned)tr.historyLength : 4u;
-                unsigned wsum = 0, hsum = 0;
-                for (unsigned k = tr.bboxes.size() - nprior; k < tr.bboxes.size(); ++k) {
-                    wsum += tr.bboxes[k].width;
-                    hsum += tr.bboxes[k].height;
-                }
-                const int w = (int)((wsum + d.width) / (nprior + 1)), h = (int)((hsum + d.height) / (nprior + 1));
-                const tbd::Rect r = tbd::rect_from_point2d((double)d.x + (d.width / 2 - w / 2),
-                                                           (double)d.y + (d.height / 2 - h / 2), w, h);
-                const int x0 = std::max(r.x, 0), y0 = std::max(r.y, 0);
-                const int x1 = std::min(r.x + r.width, c.width), y1 = std::min(r.y + r.height, c.height);
-                if (x1 - x0 < 3 || y1 - y0 < 3) continue;
-                if (!t->erow_of.insert(box_key(x0, y0, x1 - x0, y1 - y0), (int)t->erois.size())) continue;
-                t->erois.push_back(tbdk_roi{x0, y0, x1 - x0, y1 - y0});
-            }
-        }
-        if (t->erois.size() > n0) {  // the ROIs no ahead launch covered
-            const tbdk_level& L0 = P.lv[0];
-            const int r2 = early_launch(t->erois.data() + n0, (int)(t->erois.size() - n0), t->eb, (int)n0,
-                                        L0.data + (size_t)L0.pad * L0.pitch + L0.pad, L0.pitch);
-            if (r2 != TBDK_OK) return r2;
-            early_launched = true;
-        }
-        return TBDK_OK;
-    };
-    // the next frame's new-track ROIs (its detections beyond the bounds filter,
-    // as above), launched ahead over the caller's next frame into the next row
-    // set: that frame's step takes them over, so its refreshed-set PyrLK no
-    // longer waits for a GFTT launched one step before it (tbdk_tbd_run knows
-    // the next frame's detections).  Where (ctx option tbd_ahead_at): 0 right
-    // after this step's early launch, 1 after the critical PyrLK launch, 2 just
-    // before the host waits for the fit (its host work off the frame's chain)
-    bool ahead_done = false;
-    auto launch_gftt_ahead = [&](int at) -> int {
-        if (ahead_done || at < t->ctx->opt_tbd_ahead_at) return TBDK_OK;
-        ahead_done = true;
-        if (!c.use_klt || !t->ctx->opt_tbd_early_gftt) return TBDK_OK;
-        const bool all_new = t->tracker->getTracks().empty();
-        if (next && next_dets && next_ndets > 0 && t->ctx->opt_tbd_gftt_ahead && !all_new) {
-            const int nb = (t->eb + 1) % kEarlySets;
-            t->ahead_rois.clear();
-            t->ahead_row_of.clear();
-            for (int i = 0; i < next_ndets && (int)t->ahead_rois.size() < c.max_tracks; ++i) {
-                const tbdk_detection& d = next_dets[i];
-                const bool beyond = d.x >= c.bounds_xmax || d.y >= c.bounds_ymax || d.x + d.width < c.bounds_xmin ||
-                                    d.y + d.height < c.bounds_ymin;
-                if (!beyond) continue;
-                const int x0 = std::max(d.x, 0), y0 = std::max(d.y, 0);
-                const int x1 = std::min(d.x + d.width, c.width), y1 = std::min(d.y + d.height, c.height);
-                if (x1 - x0 < 3 || y1 - y0 < 3) continue;
-                if (!t->ahead_row_of.insert(box_key(x0, y0, x1 - x0, y1 - y0), (int)t->ahead_rois.size())) continue;
-                t->ahead_rois.push_back(tbdk_roi{x0, y0, x1 - x0, y1 - y0});
-            }
-            if (!t->ahead_rois.empty()) {
-                const int r2 = early_launch(t->ahead_rois.data(), (int)t->ahead_rois.size(), nb, 0, next, next_pitch);
-                if (r2 != TBDK_OK) return r2;
-                t->ahead_id = frame_id + 1;
-                t->ahead_frame = next;
-                t->ahead_pitch = next_pitch;
-                t->ahead_set = nb;
-                t->ahead_any = true;
-            }
-        }
-        return TBDK_OK;
-    };
-    // ctx option tbd_early_order: 0 launches the early GFTT first in the step, 1
-    // right after the critical (refreshed-set) PyrLK, 2 after the fit and the
-    // next pyramid, just before the host waits (its host work then runs while
-    // the device tracks; the early GFTT stream still waits for this frame's
-    // pyramid, taken above)
-    const int early_order = t->ctx->opt_tbd_early_order;
-    if (early_order == 0) {
-        rc = launch_early_gftt();
-        if (rc == TBDK_OK) rc = launch_gftt_ahead(0);
+    if (c.use_klt && t->ctx->opt_tbd_early_gftt) {
+        rc = launch_early_gftt(t, gp, P, frame_id, dets, ndets, &early_launched);
+        if (rc == TBDK_OK) rc = launch_gftt_ahead(t, gp, frame_id, next, next_pitch, next_dets, next_ndets);
         if (rc != TBDK_OK) return rc;
     }
     STEP_MARK(1);
@@ -1153,31 +1037,6 @@ int step_impl(tbdk_tbd* t, const uint8_t* frame, int pitch, int frame_id, const 
     lp.flags = 0;
     lp.min_eig_threshold = c.min_eig_threshold;
     lp.impl = 0;
-    // the look-ahead PyrLK of the n unchanged sets in h_la, pyramid A -> B, on
-    // la_s behind the look-ahead pyramid and (eig) the post-tracker GFTT's
-    // eigenvalue kernel
-    // (launch worker: posted; h_la, la_ready and eig_done are rewritten only
-    // after a drain)
-    auto launch_la = [&](int n, bool eig, tbdk_pyr& A, tbdk_pyr& B) -> int {
-        const bool wait_ready = t->la_stream != t->la_s;
-        tbdk_pyr* pa = &A;
-        tbdk_pyr* pb = &B;
-        return run_or_post(t, [t, n, eig, wait_ready, lp, pa, pb]() -> int {
-            hipStream_t ls = t->la_s;
-            hipError_t e = wait_ready ? wait_if_pending(ls, t->la_ready) : hipSuccess;
-            if (e == hipSuccess && eig) e = wait_if_pending(ls, t->eig_done);
-            if (e == hipSuccess && !t->zc)
-                e = hipMemcpyAsync(t->d_la, t->h_la, sizeof(int32_t) * n, hipMemcpyHostToDevice, ls);
-            if (e != hipSuccess) return map_status(e);
-            const int r = loop_lk(t, pa, pb, n * kSlotPts, lp, ls, t->d_la, t->h_la);
-            if (r != TBDK_OK) return r;
-            return map_status(hipEventRecord(t->la_done, ls));
-        });
-    };
-    // the previous step's deferred look-ahead PyrLK (ctx option tbd_la_defer),
-    // launched below once this step's critical PyrLK is; dropped with the look-ahead
-    const int la_defer = la_lk ? t->la_defer_n : 0;
-    t->la_defer_n = 0;
     if (run_klt) {
         for (const auto& tr : tracks) {
             const int* it = t->slot_of.find(tr.id);
@@ -1216,7 +1075,6 @@ int step_impl(tbdk_tbd* t, const uint8_t* frame, int pitch, int frame_id, const 
     for (int sl : t->src_list) t->src_row[(size_t)sl] = -1;  // the fit compacts them into their slots
     t->src_list.clear();
 
-
     STEP_MARK(2);
     std::fill(t->refreshed.begin(), t->refreshed.end(), 0);
     {  // the previous step's early and post-tracker GFTT (their rows) before the refreshed sets
@@ -1229,10 +1087,6 @@ int step_impl(tbdk_tbd* t, const uint8_t* frame, int pitch, int frame_id, const 
     // overwrites), beside the fit, so the look-ahead PyrLK that follows it on
     // that stream needs no cross-stream edge
     auto enqueue_next_pyr = [&](bool side, bool wait = true) -> int {
-        // the posted look-ahead launches first (they read la_ready; in stream
-        // order on la_s ahead of this build, as without the worker)
-        const int dr = drain(t);
-        if (dr != TBDK_OK) return dr;
         hipStream_t ps = s;
         if (side) {
             ps = t->la_s;
@@ -1255,10 +1109,6 @@ int step_impl(tbdk_tbd* t, const uint8_t* frame, int pitch, int frame_id, const 
             rc = loop_lk(t, &Pprev, &P, nsets * kSlotPts, lp, s, t->d_lists + first, t->h_lists + first);
             if (rc != TBDK_OK) return rc;
         }
-        if (la_defer > 0) {
-            rc = launch_la(la_defer, t->la_defer_eig, Pprev, P);
-            if (rc != TBDK_OK) return rc;
-        }
         // tbd_la_pyr_side 2: the look-ahead pyramid now, on the look-ahead
         // stream with no wait: its buffer held the pyramid of two frames back,
         // whose last readers (the previous step's PyrLK, the GFTT before it)
@@ -1269,18 +1119,8 @@ int step_impl(tbdk_tbd* t, const uint8_t* frame, int pitch, int frame_id, const 
             pyr_enqueued = true;
         }
         STEP_MARK(3);
-        if (early_order == 1) {
-            rc = launch_early_gftt();
-            if (rc != TBDK_OK) return rc;
-        }
-        if (early_order <= 1) {
-            rc = launch_gftt_ahead(1);
-            if (rc != TBDK_OK) return rc;
-        }
         hipError_t e = hipSuccess;  // zero-copy without a look-ahead wait sets it nowhere below
         if (la_lk) {  // the fit reads the look-ahead PyrLK's results
-            rc = drain(t);
-            if (rc != TBDK_OK) return rc;
             if (t->ctx->opt_tbd_fit_gate) {
                 // ctx option tbd_fit_gate: the host waits for the look-ahead PyrLK
                 // and then launches the fit behind this step's PyrLK on the same
@@ -1336,12 +1176,6 @@ int step_impl(tbdk_tbd* t, const uint8_t* frame, int pitch, int frame_id, const 
             rc = enqueue_next_pyr(pyr_side);
             if (rc != TBDK_OK) return rc;
         }
-        if (early_order == 2) {
-            rc = launch_early_gftt();
-            if (rc != TBDK_OK) return rc;
-        }
-        rc = launch_gftt_ahead(2);
-        if (rc != TBDK_OK) return rc;
         auto ts0 = clk::now();
         STEP_MARK(4);
         launch_us = std::chrono::duration<double, std::micro>(ts0 - t_step0).count() - gate_us;
@@ -1411,8 +1245,6 @@ int step_impl(tbdk_tbd* t, const uint8_t* frame, int pitch, int frame_id, const 
         // host tracks; the post-tracker phase adds the unchanged sets it missed
         if (next && t->ctx->opt_tbd_spec_la && frame_id % c.redetect_every != 0) {
             SUB_START();
-            rc = drain(t);  // h_spec is rewritten below
-            if (rc != TBDK_OK) return rc;
             int ns = 0;
             k = 0;
             for (const auto& tr : tracks) {
@@ -1430,20 +1262,7 @@ int step_impl(tbdk_tbd* t, const uint8_t* frame, int pitch, int frame_id, const 
             }
             SUB_MARK(0);
             if (ns > 0) {
-                // (launch worker: posted, so the tracker step below starts now)
-                const bool wait_ready = t->la_stream != t->la_s;
-                tbdk_pyr* pa = &P;
-                tbdk_pyr* pb = &Pnext;
-                rc = run_or_post(t, [t, ns, wait_ready, lp, pa, pb]() -> int {
-                    hipStream_t ls = t->la_s;
-                    hipError_t e2 = wait_ready ? wait_if_pending(ls, t->la_ready) : hipSuccess;
-                    if (e2 == hipSuccess && !t->zc)
-                        e2 = hipMemcpyAsync(t->d_spec, t->h_spec, sizeof(int32_t) * ns, hipMemcpyHostToDevice, ls);
-                    if (e2 != hipSuccess) return map_status(e2);
-                    const int r = loop_lk(t, pa, pb, ns * kSlotPts, lp, ls, t->d_spec, t->h_spec);
-                    if (r != TBDK_OK) return r;
-                    return map_status(hipEventRecord(t->la_done, ls));
-                });
+                rc = launch_la_lk(t, lp, &P, &Pnext, ns, t->d_spec, t->h_spec, nullptr);
                 if (rc != TBDK_OK) return rc;
                 SUB_MARK(3);
                 for (int q = 0; q < ns; ++q) {
@@ -1468,44 +1287,24 @@ int step_impl(tbdk_tbd* t, const uint8_t* frame, int pitch, int frame_id, const 
         const int ela = t->ctx->opt_tbd_early_la;
         const int ne = (int)t->erois.size();
         if (next && early_launched && ne > 0 && (ela >= 2 || (ela == 1 && frame_id % c.redetect_every == 0))) {
-            rc = drain(t);  // la_s and la_done from this thread below
-            if (rc != TBDK_OK) return rc;
             for (int q = 0; q < ne; ++q) t->h_ers[q] = erow0 + q;
-            hipStream_t ls = t->la_s;
-            e = t->la_stream == ls ? hipSuccess : wait_if_pending(ls, t->la_ready);
-            if (e == hipSuccess) e = wait_if_pending(ls, t->early_done[t->eb]);
-            if (e == hipSuccess && !t->zc)
-                e = hipMemcpyAsync(t->d_ers, t->h_ers, sizeof(int32_t) * ne, hipMemcpyHostToDevice, ls);
-            if (e != hipSuccess) return map_status(e);
-            rc = loop_lk(t, &P, &Pnext, ne * kSlotPts, lp, ls, t->d_ers, t->h_ers);
+            rc = launch_la_lk(t, lp, &P, &Pnext, ne, t->d_ers, t->h_ers, t->early_done[t->eb]);
             if (rc != TBDK_OK) return rc;
-            e = hipEventRecord(t->la_done, ls);
-            if (e != hipSuccess) return map_status(e);
             for (int q = 0; q < ne; ++q) {
                 t->ers_row[(size_t)(erow0 + q)] = 1;
                 t->ers_list.push_back(erow0 + q);
             }
             t->la_lk = true;
         }
-    } else {
-        if (early_order != 0) {
-            rc = launch_early_gftt();
-            if (rc != TBDK_OK) return rc;
+    } else if (next) {
+        // the next pyramid is rebuilt over the previous frame's, which the
+        // previous step's look-ahead PyrLK (on la_s) may still be reading
+        if (had_la_lk) {
+            hipError_t e = wait_if_pending(s, t->la_done);
+            if (e != hipSuccess) return map_status(e);
         }
-        rc = launch_gftt_ahead(2);
+        rc = enqueue_next_pyr(false);
         if (rc != TBDK_OK) return rc;
-        if (next) {
-            // the next pyramid is rebuilt over the previous frame's, which the
-            // previous step's look-ahead PyrLK (on la_s) may still be reading
-            if (had_la_lk) {
-                rc = drain(t);
-                if (rc != TBDK_OK) return rc;
-                hipError_t e = wait_if_pending(s, t->la_done);
-                if (e != hipSuccess) return map_status(e);
-            }
-            rc = enqueue_next_pyr(false);
-            if (rc != TBDK_OK) return rc;
-        }
     }
 
     STEP_MARK(7);
@@ -1633,15 +1432,8 @@ int step_impl(tbdk_tbd* t, const uint8_t* frame, int pitch, int frame_id, const 
                 // on la_s, after the fit and the pyramid (la_ready) and behind the
                 // GFTT eigenvalue kernel: its many large workgroups would otherwise
                 // wait for the long-lived PyrLK waves to drain
-                if (t->ctx->opt_tbd_la_defer) {
-                    // launched by the next step right after its critical PyrLK
-                    // (off the host chain between this fit and that launch)
-                    t->la_defer_n = n;
-                    t->la_defer_eig = nroi > 0;
-                } else {
-                    rc = launch_la(n, nroi > 0, P, Pnext);
-                    if (rc != TBDK_OK) return rc;
-                }
+                rc = launch_la_lk(t, lp, &P, &Pnext, n, t->d_la, t->h_la, nroi > 0 ? t->eig_done : nullptr);
+                if (rc != TBDK_OK) return rc;
                 t->la_lk = true;
             }
         }
@@ -1691,14 +1483,6 @@ int step_impl(tbdk_tbd* t, const uint8_t* frame, int pitch, int frame_id, const 
     return TBDK_OK;
 }
 
-// every public call returns with all of its work enqueued (the launch worker's
-// queue drained): the caller may synchronise its streams or the device
-int finish(tbdk_tbd* t, int rc)
-{
-    const int d = t ? drain(t) : TBDK_OK;
-    return rc != TBDK_OK ? rc : d;
-}
-
 }  // namespace
 
 extern "C" {
@@ -1728,16 +1512,15 @@ int tbdk_probe_step_profile(double* out, int cap)
 int tbdk_tbd_step(tbdk_tbd* t, const uint8_t* frame, int pitch, int frame_id, const tbdk_detection* dets,
                   int ndets, tbdk_frame_metrics* metrics, void* stream)
 {
-    return finish(t, step_impl(t, frame, pitch, frame_id, dets, ndets, nullptr, 0, metrics,
-                               static_cast<hipStream_t>(stream)));
+    return step_impl(t, frame, pitch, frame_id, dets, ndets, nullptr, 0, metrics, static_cast<hipStream_t>(stream));
 }
 
 int tbdk_tbd_step_ahead(tbdk_tbd* t, const uint8_t* frame, int pitch, int frame_id, const tbdk_detection* dets,
                         int ndets, const uint8_t* next_frame, int next_pitch, tbdk_frame_metrics* metrics,
                         void* stream)
 {
-    return finish(t, step_impl(t, frame, pitch, frame_id, dets, ndets, next_frame, next_pitch, metrics,
-                               static_cast<hipStream_t>(stream)));
+    return step_impl(t, frame, pitch, frame_id, dets, ndets, next_frame, next_pitch, metrics,
+                     static_cast<hipStream_t>(stream));
 }
 
 int tbdk_tbd_run(tbdk_tbd* t, const uint8_t* const* frames, int pitch, int first_frame_id,
@@ -1774,16 +1557,14 @@ int tbdk_tbd_run(tbdk_tbd* t, const uint8_t* const* frames, int pitch, int first
                            det_offsets[i + 1] - det_offsets[i], next, pitch, metrics ? metrics + i : nullptr, s,
                            nd ? dets + det_offsets[i + 1] : nullptr, nd ? det_offsets[i + 2] - det_offsets[i + 1] : -1);
         if (rc != TBDK_OK) {
-            (void)finish(t, TBDK_OK);
             (void)end_ahead();
             (void)end_borrow(t, s);
             return rc;
         }
     }
-    const int rc = finish(t, TBDK_OK);
     const int ra = end_ahead();
     const int rb = end_borrow(t, s);
-    return rc != TBDK_OK ? rc : ra != TBDK_OK ? ra : rb;
+    return ra != TBDK_OK ? ra : rb;
 }
 
 int tbdk_tbd_run_host(tbdk_tbd* t, const uint8_t* const* frames, int pitch, int first_frame_id,
@@ -1836,11 +1617,11 @@ int tbdk_tbd_run_host(tbdk_tbd* t, const uint8_t* const* frames, int pitch, int 
         int rc = step_impl(t, t->ring[i % 3], t->ring_pitch, first_frame_id + i,
                            dets ? dets + det_offsets[i] : nullptr, det_offsets[i + 1] - det_offsets[i], next,
                            t->ring_pitch, metrics ? metrics + i : nullptr, s);
-        if (rc != TBDK_OK) return finish(t, rc);
+        if (rc != TBDK_OK) return rc;
         e = hipEventRecord(t->freed[i % 3], s);
-        if (e != hipSuccess) return finish(t, map_status(e));
+        if (e != hipSuccess) return map_status(e);
     }
-    return finish(t, TBDK_OK);
+    return TBDK_OK;
 }
 
 int tbdk_tbd_predictions(const tbdk_tbd* t, tbdk_prediction* out, int cap, int* n)
@@ -1860,7 +1641,6 @@ int tbdk_tbd_tracks(tbdk_tbd* t, tbdk_track_info* out, int cap, int* n)
     if (!t || !n || cap < 0 || (cap > 0 && !out)) return TBDK_EINVAL;
     const auto& tracks = t->tracker->getTracks();
     std::vector<int32_t> counts(kRowSets * (size_t)t->cfg.max_tracks);  // slots and GFTT rows
-    if (const int d = drain(t)) return d;
     (void)hipSetDevice(t->ctx->device);
     hipError_t e = hipStreamSynchronize(t->side);  // post-tracker work (behind the early GFTT) runs on `side`
     if (e == hipSuccess && t->early_s) e = hipStreamSynchronize(t->early_s);  // the early GFTT rows (tbd_post_direct)

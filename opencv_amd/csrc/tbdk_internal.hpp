@@ -75,12 +75,13 @@ struct tbdk_ctx {
     int device = 0;
     std::atomic<bool> timing{false};
     // guards the timing state below (timing_only, timing_calls, recs,
-    // free_events): a TBD loop's launch worker records launches too
+    // free_events): loops stepped from different host threads on one context
+    // record launches concurrently
     std::mutex timing_mu;
     int opt_gftt_eig_redo = 0;  // tbdk_ctx_set_option("gftt_eig_redo")
     int opt_pyr_xcd = 1;       // tbdk_ctx_set_option("pyr_xcd"): pyramid roles' row bands per XCD
     int opt_pyr_rows = 1;      // tbdk_ctx_set_option("pyr_rows"): rows per thread of the two-role u8 build (1, 2, 4)
-    int opt_pyr_fuse = 1;      // tbdk_ctx_set_option("pyr_fuse"): 1 the two-role launch + one per level, 2 levels 0-2 in one tiled launch (slower, A/B), 0 one launch per level
+    int opt_pyr_fuse = 1;      // tbdk_ctx_set_option("pyr_fuse"): 1 the two-role launch + one per level, 0 one launch per level
     int opt_lk_solo = 4;       // tbdk_ctx_set_option("lk_solo"): LkArgs::solo_min of the lk_multi launches
     int opt_lk_scharr_fly = 0; // tbdk_ctx_set_option("lk_scharr_fly"): lk_multi derives Ix/Iy itself
     int opt_lk_impl = 0;        // tbdk_ctx_set_option("lk_impl"): PyrLK kernel under impl 0
@@ -93,8 +94,6 @@ struct tbdk_ctx {
     int opt_tbd_spec_la = 1;     // tbdk_ctx_set_option("tbd_spec_lookahead")
     int opt_tbd_zero_copy = 1;   // tbdk_ctx_set_option("tbd_zero_copy"), read by tbdk_tbd_create
     int opt_tbd_fit_flag = 1;    // tbdk_ctx_set_option("tbd_fit_flag"), read by tbdk_tbd_create
-    int opt_tbd_early_order = 0;  // tbdk_ctx_set_option("tbd_early_order"): where the early GFTT is launched in a step (round 6: 0)
-    int opt_tbd_early_prio = 0;  // tbdk_ctx_set_option("tbd_early_prio"), read by tbdk_tbd_create
     int opt_tbd_early_la = 1;    // tbdk_ctx_set_option("tbd_early_la"): look-ahead PyrLK of early GFTT rows
     int opt_tbd_pyr_derivs = 0;  // tbdk_ctx_set_option("tbd_pyr_derivs"): loop pyramids with Scharr planes (A/B)
     int opt_tbd_fit_inline = 1;  // tbdk_ctx_set_option("tbd_fit_inline"): the fit table in the kernel arguments
@@ -102,15 +101,12 @@ struct tbdk_ctx {
     int opt_tbd_fit_wgpub = 1;   // tbdk_ctx_set_option("tbd_fit_wgpub"): one system-scope release per fit workgroup
     int opt_tbd_la_pyr_side = 2;  // tbdk_ctx_set_option("tbd_la_pyr_side"): where the look-ahead pyramid is built
     int opt_tbd_post_direct = 1;  // tbdk_ctx_set_option("tbd_post_direct"): next step waits for the early GFTT itself
-    int opt_tbd_la_defer = 0;    // tbdk_ctx_set_option("tbd_la_defer"): look-ahead PyrLK launched by the next step
     int opt_gftt_compact = 1;    // tbdk_ctx_set_option("gftt_compact"): GFTT writes only its candidates' values
-    int opt_tbd_ahead_at = 0;    // tbdk_ctx_set_option("tbd_ahead_at"): where a step launches the ahead GFTT (0..2)
     int opt_tbd_gftt_ahead = 1;  // tbdk_ctx_set_option("tbd_gftt_ahead"): tbdk_tbd_run's early GFTT a frame ahead
     int opt_tbd_borrow_l0 = 0;   // tbdk_ctx_set_option("tbd_borrow_l0"): tbdk_tbd_run's pyramids take the frame as level 0 (A/B)
     int opt_tbd_fit_gate = 1;    // tbdk_ctx_set_option("tbd_fit_gate"): the host launches the fit once the look-ahead PyrLK is done
     int opt_tbd_fit_ransac = 0;  // tbdk_ctx_set_option("tbd_fit_ransac"): RANSAC rounds of the loop's fit, 0 = least squares (read by tbdk_tbd_create)
     int opt_tbd_fb_check = 0;    // tbdk_ctx_set_option("tbd_fb_check"): the loop's forward-backward check, threshold in 1/1024 px, 0 = off (read by tbdk_tbd_create)
-    int opt_tbd_async_la = 0;    // tbdk_ctx_set_option("tbd_async_la"): look-ahead launches by a worker thread (read by tbdk_tbd_create)
     std::string timing_only;  // ",name,name," filter of tbdk_timing_select ("" = all)
     int timing_every = 1;     // tbdk_ctx_set_option("timing_every"): events on every Nth selected launch
     std::vector<std::pair<std::string, int64_t>> timing_calls;  // selected launches per name (sampled or not)

@@ -35,7 +35,7 @@ _BOUNDS = ("bounds_xmin", "bounds_xmax", "bounds_ymin", "bounds_ymax")
 CTX_DEFAULTS = {
     "lk_impl": 0, "lk_scharr_fly": 0, "lk_seg_inline": 1, "lk_solo": 4, "pyr_fuse": 1, "gftt_inline": 1,
     "gftt_compact": 1, "tbd_pyr_derivs": 0, "tbd_zero_copy": 1, "tbd_fit_inline": 1, "tbd_fit_flag": 1,
-    "tbd_async_la": 0, "tbd_la_defer": 0, "tbd_early_gftt": 2, "tbd_borrow_l0": 0, "tbd_spec_lookahead": 1,
+    "tbd_early_gftt": 2, "tbd_borrow_l0": 0, "tbd_spec_lookahead": 1,
     "tbd_early_la": 1, "tbd_gftt_ahead": 1,
 }
 
@@ -239,8 +239,6 @@ CASES = [
     _case("w9_staged_tables", _W9, {"tbd_zero_copy": 0}),
     _case("w9_table_args", _W9, {"tbd_fit_inline": 0, "gftt_inline": 0}),
     _case("w9_gftt_full", _W9, {"gftt_compact": 0}),
-    _case("w9_async_la", _W9, {"tbd_async_la": 1}),
-    _case("w9_la_defer", _W9, {"tbd_la_defer": 1}),
     _case("w9_no_early_gftt", _W9, {"tbd_early_gftt": 0}),
 ]
 CASE_IDS = [c.id for c in CASES]

@@ -193,15 +193,11 @@ def test_tbd_early_gftt_matches_post_tracker_gftt(gpu, api):
     c = tbd.default_config(W, H, bounds_xmax=640, bounds_ymax=360, redetect_every=4)
     res = {}
     try:
-        for early, spec, ela, order, prio in ((2, 1, 1, 0, 0), (2, 1, 0, 0, 0), (2, 1, 2, 0, 0), (2, 0, 1, 0, 0),
-                                              (1, 1, 1, 0, 0), (1, 1, 2, 0, 0), (1, 0, 1, 0, 0), (0, 1, 1, 0, 0),
-                                              (0, 0, 0, 0, 0), (2, 1, 1, 1, 0), (2, 1, 1, 2, 0), (1, 0, 2, 2, 0),
-                                              (2, 1, 1, 1, 1), (2, 1, 1, 0, 1)):
+        for early, spec, ela in ((2, 1, 1), (2, 1, 0), (2, 1, 2), (2, 0, 1), (1, 1, 1), (1, 1, 2), (1, 0, 1),
+                                 (0, 1, 1), (0, 0, 0)):
             gpu.set_option("tbd_early_gftt", early)
             gpu.set_option("tbd_spec_lookahead", spec)
             gpu.set_option("tbd_early_la", ela)
-            gpu.set_option("tbd_early_order", order)  # where the step launches the early GFTT
-            gpu.set_option("tbd_early_prio", prio)  # its stream's priority (read by the loop's creation)
             loop = tbd.TbdLoop(c, ctx=gpu)
             ms, preds = [], []
             if api == "run":
@@ -211,22 +207,18 @@ def test_tbd_early_gftt_matches_post_tracker_gftt(gpu, api):
                     nxt = frames[f + 1] if api == "ahead" and f + 1 < F else None
                     ms.append(loop.step(frames[f], f, dets[f], next_frame=nxt))
                     preds.append(loop.predictions())
-            res[early, spec, ela, order, prio] = ([_mkey(m) for m in ms], preds, loop.tracks(),
-                                            sum(m.early_gftt for m in ms))
+            res[early, spec, ela] = ([_mkey(m) for m in ms], preds, loop.tracks(), sum(m.early_gftt for m in ms))
     finally:
         gpu.set_option("tbd_early_gftt", 2)
         gpu.set_option("tbd_spec_lookahead", 1)
         gpu.set_option("tbd_early_la", 1)
-        gpu.set_option("tbd_early_order", 0)  # the default
-        gpu.set_option("tbd_early_prio", 0)
-    base = res[0, 0, 0, 0, 0]
+    base = res[0, 0, 0]
     for key, r in res.items():
         assert r[0] == base[0], key
         assert r[1] == base[1], key
         assert r[2] == base[2], key
-    assert res[1, 1, 1, 0, 0][3] > 2 * F and base[3] == 0  # the early path was taken (and off means off)
-    assert res[2, 1, 1, 0, 0][3] > res[1, 1, 1, 0, 0][3] + F  # re-detection guesses confirmed
-    assert res[2, 1, 1, 1, 0][3] == res[2, 1, 1, 2, 0][3] == res[2, 1, 1, 0, 0][3] == res[2, 1, 1, 1, 1][3]
+    assert res[1, 1, 1][3] > 2 * F and base[3] == 0  # the early path was taken (and off means off)
+    assert res[2, 1, 1][3] > res[1, 1, 1][3] + F  # re-detection guesses confirmed
 
 
 def test_tbd_zero_copy_matches_copies(gpu):
@@ -285,12 +277,12 @@ def test_tbd_fit_flag_matches_event(gpu):
         assert r == res[0]
 
 
-def test_tbd_deferred_lookahead_matches(gpu):
-    """The look-ahead PyrLK of the unchanged sets launched by the next step
-    right after its critical PyrLK (ctx option tbd_la_defer), and the
-    look-ahead pyramid built on the look-ahead stream (tbd_la_pyr_side), give
-    the same frames as the defaults, through tbdk_tbd_run and per-frame steps
-    with and without an announced next frame."""
+def test_tbd_lookahead_pyramid_stream_matches(gpu):
+    """The look-ahead pyramid built on the caller's stream or on the look-ahead
+    stream (ctx option tbd_la_pyr_side), and the next step waiting for the
+    early GFTT directly or through the post-tracker stream (tbd_post_direct),
+    give the same frames as the defaults, through tbdk_tbd_run and per-frame
+    steps with and without an announced next frame."""
     from opencv_amd import klt, tbd
 
     W, H, N, F = 960, 540, 40, 16
@@ -299,8 +291,7 @@ def test_tbd_deferred_lookahead_matches(gpu):
     c = tbd.default_config(W, H, bounds_xmax=W, bounds_ymax=H, redetect_every=4)
     res = []
     try:
-        for d, side, pd in ((0, 0, 1), (1, 0, 1), (0, 1, 1), (1, 1, 1), (0, 2, 1), (1, 2, 1), (0, 2, 0)):
-            gpu.set_option("tbd_la_defer", d)
+        for side, pd in ((0, 1), (1, 1), (2, 1), (2, 0)):
             gpu.set_option("tbd_la_pyr_side", side)
             gpu.set_option("tbd_post_direct", pd)
             loop = tbd.TbdLoop(c, ctx=gpu)
@@ -312,7 +303,6 @@ def test_tbd_deferred_lookahead_matches(gpu):
                 mt.append(_mkey(stepped.step(frames[f], f, dets[f], next_frame=nxt)))
             res.append(([_mkey(m) for m in ms], loop.tracks(), mt, stepped.tracks()))
     finally:
-        gpu.set_option("tbd_la_defer", 0)
         gpu.set_option("tbd_la_pyr_side", 2)  # the default
         gpu.set_option("tbd_post_direct", 1)
     for r in res[1:]:
@@ -419,49 +409,6 @@ def test_tbd_lookahead_then_no_tracks(gpu):
     assert nt[-1] > 0 and sum(m[7] for m in base[0][27:]) > 0  # tracking resumed after the gap
 
 
-def test_tbd_async_launch_worker_matches(gpu):
-    """The look-ahead PyrLK launches issued by the loop's launch worker thread
-    (ctx option tbd_async_la, read at loop creation) and by the loop's own
-    thread give the same frames, through tbdk_tbd_run and per-frame steps with
-    and without an announced next frame, with and without the deferred
-    look-ahead; with timing events on, the worker's launches are recorded
-    beside the loop thread's (the context's timing state is shared)."""
-    from opencv_amd import klt, tbd
-
-    W, H, N, F = 960, 540, 40, 16
-    frames, gt = klt.synth_render(13, W, H, N, 0, F, ctx=gpu)
-    dets = [tbd.detections_from_gt(gt[f].numpy()) for f in range(F)]
-    c = tbd.default_config(W, H, bounds_xmax=640, bounds_ymax=360, redetect_every=4)
-    res = []
-    try:
-        for asy, d in ((0, 0), (1, 0), (1, 1)):
-            gpu.set_option("tbd_async_la", asy)
-            gpu.set_option("tbd_la_defer", d)
-            gpu.timing_select(["lk_sparse"])
-            gpu.timing_enable(True)
-            loop = tbd.TbdLoop(c, ctx=gpu)
-            ms = loop.run(frames, 0, dets)
-            n_lk, _ = gpu.timing_query("lk_sparse")
-            gpu.timing_enable(False)
-            gpu.timing_select(None)
-            stepped = tbd.TbdLoop(c, ctx=gpu)
-            mt = []
-            for f in range(F):
-                nxt = frames[f + 1] if f + 1 < F and f % 3 != 2 else None
-                mt.append(_mkey(stepped.step(frames[f], f, dets[f], next_frame=nxt)))
-            res.append(([_mkey(m) for m in ms], loop.tracks(), mt, stepped.tracks(), n_lk))
-            del loop, stepped
-    finally:
-        gpu.set_option("tbd_async_la", 0)
-        gpu.set_option("tbd_la_defer", 0)
-        gpu.timing_enable(False)
-        gpu.timing_select(None)
-    for r in res[1:]:
-        assert r[:4] == res[0][:4]
-    assert res[0][4] > F and res[1][4] == res[0][4]  # every PyrLK launch timed, the worker's included
-
-
-
 def test_tbd_run_borrowed_level0_matches_copy(gpu):
     """tbdk_tbd_run's pyramids taking the caller's frame as level 0 (ctx option
     tbd_borrow_l0, A/B: no padded copy; PyrLK reads windows across the
@@ -532,9 +479,8 @@ def test_tbd_run_gftt_ahead_matches(gpu):
     c = tbd.default_config(W, H, bounds_xmax=640, bounds_ymax=360, redetect_every=3)
     res = []
     try:
-        for ahead, at in ((0, 2), (1, 0), (1, 1), (1, 2)):
+        for ahead in (0, 1):
             gpu.set_option("tbd_gftt_ahead", ahead)
-            gpu.set_option("tbd_ahead_at", at)  # where the step launches it
             loop = tbd.TbdLoop(c, ctx=gpu)
             ms = loop.run(frames, 0, dets)
             split = tbd.TbdLoop(c, ctx=gpu)
@@ -545,10 +491,28 @@ def test_tbd_run_gftt_ahead_matches(gpu):
             del loop, split
     finally:
         gpu.set_option("tbd_gftt_ahead", 1)
-        gpu.set_option("tbd_ahead_at", 0)
     stepped = tbd.TbdLoop(c, ctx=gpu)
     ref = [_mkey(stepped.step(frames[f], f, dets[f])) for f in range(F)]
     assert sum(k[10] for k in ref) > F  # re-detections / new tracks every frame
     for r in res:
         assert r[0] == ref and r[2] == ref
         assert r[1] == stepped.tracks() and r[3] == stepped.tracks()
+
+
+def test_retired_context_options_are_rejected(gpu):
+    """The names of the removed A/B switches are unknown options (TBDK_EINVAL,
+    as for any other unknown name), and pyr_fuse takes 0 and 1 only: its value
+    2, the one-launch build of three levels, is gone.  No kernel is launched."""
+    from opencv_amd import _lib
+
+    for name in ("tbd_async_la", "tbd_la_defer", "tbd_early_order", "tbd_ahead_at", "tbd_early_prio"):
+        for value in (0, 1):
+            with pytest.raises(_lib.TbdkError, match="TBDK_EINVAL"):
+                gpu.set_option(name, value)
+    try:
+        with pytest.raises(_lib.TbdkError, match="TBDK_EINVAL"):
+            gpu.set_option("pyr_fuse", 2)
+        gpu.set_option("pyr_fuse", 0)
+        gpu.set_option("pyr_fuse", 1)
+    finally:
+        gpu.set_option("pyr_fuse", 1)

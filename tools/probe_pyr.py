@@ -1,5 +1,5 @@
-"""tbdk_pyr_build timing by ctx options pyr_fuse (2: levels 0-2 in one tiled
-launch, 1: the two-role launch + one per level, 0: one launch per level) and
+"""tbdk_pyr_build timing by ctx options pyr_fuse (1: the two-role launch +
+one per level, 0: one launch per level) and
 pyr_rows (rows per thread of the two-role launch) and pyr_xcd (row bands per
 XCD), levels-only and with
 derivative planes, 1080p / KITTI / 4K.  HIP events over 100 builds per
@@ -24,9 +24,9 @@ def opt(name, v):
         pass
 
 
-VARIANTS = [("tiled", False, 2, 4, 1), ("two-role r4", False, 1, 4, 1), ("two-role r4 noxcd", False, 1, 4, 0),
-            ("two-role r2", False, 1, 2, 1), ("two-role r1", False, 1, 1, 1), ("two-role r1 noxcd", False, 1, 1, 0),
-            ("per level", False, 0, 4, 1), ("planes two-role r4", True, 1, 4, 1)]
+VARIANTS = [("two-role r4", False, 1, 4, 1), ("two-role r4 noxcd", False, 1, 4, 0), ("two-role r2", False, 1, 2, 1),
+            ("two-role r1", False, 1, 1, 1), ("two-role r1 noxcd", False, 1, 1, 0), ("per level", False, 0, 4, 1),
+            ("planes two-role r4", True, 1, 4, 1)]
 
 
 def timed(P, frames, n=100):

@@ -1,4 +1,4 @@
-"""Floating-point pyramid build timing by ctx option pyr_fuse (>= 1: the
+"""Floating-point pyramid build timing by ctx option pyr_fuse (1: the
 role-split build of klt_pyr_fp.hip, 0: one launch per plane): fp16 levels from
 u8 / fp16 frames and fp32 levels from u8 / fp32 frames, 1080p and 4K, HIP events
 over 100 builds each; with each build's minimal HBM bytes (frame read once,
