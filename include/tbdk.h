@@ -472,6 +472,32 @@ int tbdk_gftt_rois(tbdk_ctx* ctx, const uint8_t* img, int width, int height, int
                    const tbdk_roi* rois, int nroi, const tbdk_gftt_params* params,
                    float* corners, int32_t* counts, void* stream);
 
+/* tbdk_gftt_rois under an arbitrary 8-bit mask: goodFeaturesToTrack's `mask`
+ * argument (featureselect.cpp:361-516; CornersDetector::detect's, gftt.cpp:98).
+ *   mask       : device u8 plane, width x height in the image's coordinates,
+ *                rows mask_pitch bytes apart (>= width), no alignment
+ *                requirement on pointer or pitch; ROI r reads
+ *                mask + r.y * mask_pitch + r.x.  NULL: tbdk_gftt_rois exactly.
+ * Per ROI the result is the CPU goodFeaturesToTrack on the ROI as an isolated
+ * image with the mask cropped to the same rectangle:
+ *   - the response map does not depend on the mask;
+ *   - maxVal is the maximum of the response over the ROI's pixels (border
+ *     pixels included) whose mask byte is non-zero (any of 1..255), 0 when
+ *     there is none (minMaxIdx under an empty mask) -- such a ROI has 0 corners;
+ *   - the threshold at (float)(maxVal * quality_level) and the 3x3 dilation run
+ *     over every pixel of the ROI: a masked-out neighbour with a larger
+ *     response still suppresses a masked-in pixel;
+ *   - a candidate is an interior pixel with val != 0, val == dilated and a
+ *     non-zero mask byte; sort, min-distance walk and max_corners as unmasked;
+ *   - counts[i] = -1 only when the candidates that pass the mask exceed the
+ *     on-chip capacity.
+ * So the corners differ from those of an unmasked call filtered by the mask.
+ * TBDK_EINVAL for mask != NULL && mask_pitch < width. */
+int tbdk_gftt_rois_masked(tbdk_ctx* ctx, const uint8_t* img, int width, int height, int pitch,
+                          const uint8_t* mask, int mask_pitch,
+                          const tbdk_roi* rois, int nroi, const tbdk_gftt_params* params,
+                          float* corners, int32_t* counts, void* stream);
+
 /* cv::cuda::createMinEigenValCorner(CV_8UC1, blockSize 3, ksize 3,
  * BORDER_REFLECT_101)->compute(src, dst) (cudaimgproc/src/corners.cpp:150-189,
  * cudaimgproc.hpp:564): the minimum-eigenvalue map GFTT selects from, with
@@ -948,6 +974,13 @@ int tbdk_tbd_default_config(int width, int height, tbdk_tbd_config* cfg);
  * GPU and process), and destroy every loop before its context. */
 int tbdk_tbd_create(tbdk_ctx* ctx, const tbdk_tbd_config* cfg, tbdk_tbd** out);
 int tbdk_tbd_destroy(tbdk_tbd* tbd);
+/* A static corner mask for the loop's GFTT launches (tbdk_gftt_rois_masked's
+ * semantics): a device u8 plane of the loop's frame size (cfg.width x
+ * cfg.height), rows mask_pitch bytes apart, which the caller keeps alive and
+ * unchanged for the loop's life.  NULL clears it.  Only before the loop's
+ * first step: afterwards TBDK_EINVAL, because the GFTT launched a frame ahead
+ * would have run under the old mask.  TBDK_EINVAL also for mask_pitch < width. */
+int tbdk_tbd_set_corner_mask(tbdk_tbd* tbd, const uint8_t* mask, int mask_pitch);
 /* One frame through the loop.  frame: device u8 (width x height, pitch);
  * dets: HOST array.  Synchronises the stream once (predictions -> host tracker). */
 int tbdk_tbd_step(tbdk_tbd* tbd, const uint8_t* frame, int pitch, int frame_id, const tbdk_detection* dets,

@@ -387,6 +387,15 @@ public:
         detectRois(image, &r, 1, corners, count, stream);
     }
 
+    // CornersDetector::detect(image, corners, mask, stream) (gftt.cpp:98): mask is a
+    // u8 image of the image's size; the quality threshold comes from the maximum
+    // over its non-zero pixels and only they can be corners (tbdk_gftt_rois_masked)
+    void detect(const GpuImage& image, const GpuImage& mask, float* corners, int32_t* count, void* stream = nullptr)
+    {
+        tbdk_roi r{0, 0, image.width, image.height};
+        detectRois(image, mask, &r, 1, corners, count, stream);
+    }
+
     // rois: host array; corners: device nroi x maxCorners float2; counts: device nroi int32
     void detectRois(const GpuImage& image, const tbdk_roi* rois, int nroi, float* corners, int32_t* counts,
                     void* stream = nullptr)
@@ -394,6 +403,17 @@ public:
         check(tbdk_gftt_rois(ctx_->get(), image.data, image.width, image.height, image.pitch, rois, nroi, &p_,
                              corners, counts, stream),
               "tbdk_gftt_rois");
+    }
+
+    // ... under a mask of the image's size, each ROI reading its own rectangle of it
+    void detectRois(const GpuImage& image, const GpuImage& mask, const tbdk_roi* rois, int nroi, float* corners,
+                    int32_t* counts, void* stream = nullptr)
+    {
+        if (!mask.data || mask.width != image.width || mask.height != image.height)
+            throw Error(TBDK_EINVAL, "CornersDetector: mask size");
+        check(tbdk_gftt_rois_masked(ctx_->get(), image.data, image.width, image.height, image.pitch, mask.data,
+                                    mask.pitch, rois, nroi, &p_, corners, counts, stream),
+              "tbdk_gftt_rois_masked");
     }
 
 private:

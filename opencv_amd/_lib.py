@@ -249,6 +249,9 @@ SIGNATURES = {
                                     C.c_float, C.c_void_p]),
     "tbdk_gftt_rois": (C.c_int, [C.c_void_p, C.c_void_p, C.c_int, C.c_int, C.c_int, C.POINTER(Roi), C.c_int,
                                  C.POINTER(GfttParams), C.c_void_p, C.c_void_p, C.c_void_p]),
+    "tbdk_gftt_rois_masked": (C.c_int, [C.c_void_p, C.c_void_p, C.c_int, C.c_int, C.c_int, C.c_void_p, C.c_int,
+                                        C.POINTER(Roi), C.c_int, C.POINTER(GfttParams), C.c_void_p, C.c_void_p,
+                                        C.c_void_p]),
     "tbdk_gftt_reserve": (C.c_int, [C.c_void_p, C.c_int, C.c_int64]),
     "tbdk_box_propagate": (C.c_int, [C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_int,
                                      C.c_int, C.c_void_p, C.c_void_p]),
@@ -297,6 +300,7 @@ SIGNATURES = {
     "tbdk_tbd_default_config": (C.c_int, [C.c_int, C.c_int, C.POINTER(TbdConfig)]),
     "tbdk_tbd_create": (C.c_int, [C.c_void_p, C.POINTER(TbdConfig), C.POINTER(C.c_void_p)]),
     "tbdk_tbd_destroy": (C.c_int, [C.c_void_p]),
+    "tbdk_tbd_set_corner_mask": (C.c_int, [C.c_void_p, C.c_void_p, C.c_int]),
     "tbdk_tbd_step": (C.c_int, [C.c_void_p, C.c_void_p, C.c_int, C.c_int, C.POINTER(Detection), C.c_int,
                                 C.POINTER(FrameMetrics), C.c_void_p]),
     "tbdk_tbd_step_ahead": (C.c_int, [C.c_void_p, C.c_void_p, C.c_int, C.c_int, C.POINTER(Detection), C.c_int,

@@ -24,6 +24,10 @@
 //                   step over a byte image of the ROI; in-step conflicts are
 //                   resolved in lane order so exactly the sequential walk's
 //                   corners are accepted.
+// Under a mask (goodFeaturesToTrack's `mask`, tbdk_gftt_rois_masked) the strip
+// max is taken over the masked-in pixels and gftt_select admits only masked-in
+// candidates; these are kernel instances of their own (gftt_eig_masked_kernel,
+// gftt_select_kernel<R, true>), the unmasked ones never read the mask.
 #include <atomic>
 #include <cfloat>
 #include <cmath>
@@ -152,6 +156,21 @@ struct EigLane {
     float k, k2;
 };
 
+// The corner mask of a masked launch (GfttArgs::mask), as the eigenvalue walk
+// reads it: the lane's mask byte of ROI row y, by the addressing of its image
+// byte.  Only output lanes read (they hold their own column, never a mirrored
+// one); every other lane's offset lies past the buffer, which loads 0, so halo
+// and reflected lanes never count toward the masked maximum.
+struct EigMask {
+    __amdgpu_buffer_rsrc_t rs;
+    uint32_t col;  // the lane's byte offset in a mask row, or past the buffer
+    int pitch;
+};
+__device__ __forceinline__ bool eig_mask_ld(const EigMask& m, int row)
+{
+    return __builtin_amdgcn_raw_buffer_load_b8(m.rs, m.col, row * m.pitch, 0) != 0;
+}
+
 __device__ __forceinline__ float eig_ld(const EigLane& g, int row)
 {
     return (float)__builtin_amdgcn_raw_buffer_load_b8(g.rs, g.x, row * g.pitch, 0);
@@ -195,8 +214,12 @@ __device__ __forceinline__ void eig_rowsums(const EigLane& g, const SobelRow& p,
 // local-maximum ballot, the values of its set lanes only, in lane order, at the
 // start of the strip row's own columns (column ccol + rank of the lane's bit),
 // which is all gftt_select reads when quality <= 1 (see there).
-template <bool compact, int PREF = compact ? TBDK_GFTT_EIG_PREF_C : kEigPref>
-__device__ __forceinline__ void eig_segment(const EigLane& g, float* __restrict__ E, uint64_t* __restrict__ lm,
+// masked: best is the max over the own pixels whose mask byte is non-zero (it
+// stays INT_MIN, below every float's key, when the segment has none); the
+// eigenvalues, ballots and compact values do not depend on the mask.
+template <bool compact, bool masked, int PREF = compact ? TBDK_GFTT_EIG_PREF_C : kEigPref>
+__device__ __forceinline__ void eig_segment(const EigLane& g, const EigMask& gm, float* __restrict__ E,
+                                            uint64_t* __restrict__ lm,
                                             int w, int ep, int y0, int y1, int ys, int ye, int ycap, bool fresh,
                                             double (&S)[3], double (&S0)[3], double (&Scap)[3], int& best, int ccol)
 {
@@ -231,6 +254,10 @@ __device__ __forceinline__ void eig_segment(const EigLane& g, float* __restrict_
     // in the steady rows
     auto row = [&](auto steady, int y, float cur, bool has_next, bool store, bool lmx) {
         constexpr bool ST = decltype(steady)::value;
+        bool m_in = true;  // row y's mask byte (in flight across the row's arithmetic)
+        if constexpr (masked) {
+            if (ST || store) m_in = eig_mask_ld(gm, y);
+        }
         double in[3];
         SobelRow wc = wb;
         if (ST || has_next) {  // entering cov row y + 1 (image rows y, y+1, y+2)
@@ -258,7 +285,8 @@ __device__ __forceinline__ void eig_segment(const EigLane& g, float* __restrict_
             if constexpr (!compact)
                 __builtin_amdgcn_raw_buffer_store_b32(__float_as_uint(e), rE, eoff == kDrop ? kDrop : eoff + (uint32_t)(y * ep * 4), 0, 0);
             const int kk = fkey(e);
-            best = (g.out_lane && kk > best) ? kk : best;
+            if constexpr (masked) best = (g.out_lane && m_in && kk > best) ? kk : best;
+            else best = (g.out_lane && kk > best) ? kk : best;
         }
         if (ST || lmx) {  // row y - 1's 3x3 neighbourhood is now complete
             float m = fmaxf(e2, e);
@@ -316,8 +344,8 @@ __device__ __forceinline__ void eig_segment(const EigLane& g, float* __restrict_
 
 // compact (GfttArgs::compact, see eig_segment): one instantiation per mode,
 // so each has its own register budget
-template <bool compact>
-__global__ __launch_bounds__(64 * kEigWaves) void gftt_eig_kernel(GfttArgs a)
+template <bool compact, bool masked>
+__device__ __forceinline__ void gftt_eig_body(const GfttArgs& a)
 {
     __shared__ double s_cap[kEigWaves][3][64];
     __shared__ double s_drift[3][64];
@@ -359,6 +387,13 @@ __global__ __launch_bounds__(64 * kEigWaves) void gftt_eig_kernel(GfttArgs a)
     g.pitch = a.pitch;
     g.rs = __builtin_amdgcn_make_buffer_rsrc(const_cast<uint8_t*>(a.img + (size_t)R.y * a.pitch + R.x), (short)0,
                                              a.pitch * H, 0x00020000);
+    EigMask gm{};
+    if constexpr (masked) {  // rows a.mask_pitch apart; the last row ends with the ROI
+        gm.rs = __builtin_amdgcn_make_buffer_rsrc(const_cast<uint8_t*>(a.mask + (size_t)R.y * a.mask_pitch + R.x),
+                                                  (short)0, a.mask_pitch * (H - 1) + R.w, 0x00020000);
+        gm.col = g.out_lane ? (uint32_t)g.x : 0x80000000u;
+        gm.pitch = a.mask_pitch;
+    }
     float* E = a.eig + R.off + g.x;
     // local-maximum words of this strip (ROIs of at least 3x3; never written otherwise)
     uint64_t* lm = a.lmax + R.moff + (size_t)strip * H;
@@ -391,8 +426,8 @@ __global__ __launch_bounds__(64 * kEigWaves) void gftt_eig_kernel(GfttArgs a)
     };
     GFTT_ESTAMP(0);
     if (live) {
-        eig_segment<compact>(g, E, has_lm ? lm : nullptr, R.w, gftt_epitch(R.w), y0, y1, ys, ye, ycap, true, S, S0,
-                             Scap, best, ccol);
+        eig_segment<compact, masked>(g, gm, E, has_lm ? lm : nullptr, R.w, gftt_epitch(R.w), y0, y1, ys, ye, ycap,
+                                     true, S, S0, Scap, best, ccol);
         if (ycap >= 0) {
 #pragma unroll
             for (int ch = 0; ch < 3; ++ch) s_cap[wv][ch][lane] = Scap[ch];
@@ -420,8 +455,8 @@ __global__ __launch_bounds__(64 * kEigWaves) void gftt_eig_kernel(GfttArgs a)
         __syncthreads();  // s_cap is rewritten below
         if (wv >= bad && live) {
             best = INT_MIN;
-            eig_segment<compact>(g, E, has_lm ? lm : nullptr, R.w, gftt_epitch(R.w), y0, y1, ys, ye, ycap, false, S,
-                                 S0, Scap, best, ccol);
+            eig_segment<compact, masked>(g, gm, E, has_lm ? lm : nullptr, R.w, gftt_epitch(R.w), y0, y1, ys, ye, ycap,
+                                         false, S, S0, Scap, best, ccol);
             if (ycap >= 0) {
 #pragma unroll
                 for (int ch = 0; ch < 3; ++ch) s_cap[wv][ch][lane] = Scap[ch];
@@ -444,6 +479,20 @@ __global__ __launch_bounds__(64 * kEigWaves) void gftt_eig_kernel(GfttArgs a)
         for (int k = 1; k < kEigWaves; ++k) m = s_best[k] > m ? s_best[k] : m;
         a.blk_max[blockIdx.x] = m;
     }
+}
+
+template <bool compact>
+__global__ __launch_bounds__(64 * kEigWaves) void gftt_eig_kernel(GfttArgs a)
+{
+    gftt_eig_body<compact, false>(a);
+}
+
+// the masked launch (GfttArgs::mask): a kernel of its own name, so the unmasked
+// one keeps its code and its register budget
+template <bool compact>
+__global__ __launch_bounds__(64 * kEigWaves) void gftt_eig_masked_kernel(GfttArgs a)
+{
+    gftt_eig_body<compact, true>(a);
 }
 
 // Candidate sort key: the reference order (value desc, then address desc,
@@ -867,7 +916,10 @@ __device__ uint64_t take_next64(uint64_t* rest, int nrest, int lane)
 // window rows are register arrays: radius 6 needs 156 VGPRs, radius 2 68, and
 // a select workgroup's eight waves only find room next to PyrLK waves at the
 // smaller size); the host picks the instance from min_distance.
-template <int RMAX>
+// masked (GfttArgs::mask): the ROI max is the strips' masked maxima (0 when no
+// strip has a masked-in pixel), and a candidate enters the list only when its
+// own mask byte is non-zero; threshold and dilation see every pixel.
+template <int RMAX, bool masked = false>
 __global__ __launch_bounds__(kSelThreads) void gftt_select_kernel(GfttArgs a)
 {
     extern __shared__ __attribute__((aligned(16))) uint8_t smem[];
@@ -912,10 +964,14 @@ __global__ __launch_bounds__(kSelThreads) void gftt_select_kernel(GfttArgs a)
         }
         for (; b < e; ++b) mk = a.blk_max[b] > mk ? a.blk_max[b] : mk;
     }
-    const float thr = (float)((double)fkey_inv(mk) * a.quality);
+    // masked: a strip with nothing masked in reports INT_MIN, below every float's
+    // key; the ROI with no other strip has maxVal = 0 (minMaxIdx under an empty mask)
+    const float roi_max = masked && mk == INT_MIN ? 0.f : fkey_inv(mk);
+    const float thr = (float)((double)roi_max * a.quality);
     if (tid == 0) s_total = 0;
     __syncthreads();
     const float* Ep = a.eig + R.off;
+    const uint8_t* Mp = masked ? a.mask + (size_t)R.y * a.mask_pitch + R.x : nullptr;
     if (R.w >= 3 && R.h >= 3) {
         if (thr > 0.f) {
             for (int wi = tid; wi < nw; wi += kSelThreads) {
@@ -925,10 +981,12 @@ __global__ __launch_bounds__(kSelThreads) void gftt_select_kernel(GfttArgs a)
                 const float* Er = Ep + (size_t)y * gftt_epitch(R.w) + st * kGfttStrip - kGfttHalo;
                 // compact: the word's values packed in bit order at the strip row's first columns
                 const float* Ec = Er + kGfttHalo;
+                const uint8_t* Mr = masked ? Mp + (size_t)y * a.mask_pitch + st * kGfttStrip - kGfttHalo : nullptr;
                 int rk = 0;
                 while (word) {  // up to 8 value loads in flight per round
                     int xs[8];
                     float vs[8];
+                    [[maybe_unused]] uint8_t ms[8];
 #pragma unroll
                     for (int u = 0; u < 8; ++u) {
                         xs[u] = -1;
@@ -936,11 +994,14 @@ __global__ __launch_bounds__(kSelThreads) void gftt_select_kernel(GfttArgs a)
                             xs[u] = __builtin_ctzll(word);
                             word &= word - 1ull;
                             vs[u] = a.compact ? Ec[rk++] : Er[xs[u]];
+                            if constexpr (masked) ms[u] = Mr[xs[u]];
                         }
                     }
 #pragma unroll
                     for (int u = 0; u < 8; ++u) {
-                        if (xs[u] >= 0 && vs[u] > thr) {
+                        bool in = xs[u] >= 0 && vs[u] > thr;
+                        if constexpr (masked) in = in && ms[u] != 0;
+                        if (in) {
                             const int q = atomicAdd(&s_total, 1);
                             if (q < a.cap) keys[q] = cand_key(vs[u], y, st * kGfttStrip + xs[u] - kGfttHalo);
                         }
@@ -949,13 +1010,20 @@ __global__ __launch_bounds__(kSelThreads) void gftt_select_kernel(GfttArgs a)
             }
         } else if (!a.compact) {
             // (compact mode runs with quality <= 1 only: thr = max * q >= max when
-            // max <= 0, so no value exceeds thr and the ROI has no candidate)
+            // max <= 0, so no value exceeds thr and the ROI has no candidate.
+            // Masked, with M the max over the masked-in pixels, M <= 0 and
+            // 0 < q <= 1: every masked-in v <= M <= (float)(M * q) = thr, and a
+            // candidate must be masked in, so the ROI again has none; the
+            // masked-out values above thr only suppress, which needs no list)
             const int iw = R.w - 2, n = iw * (R.h - 2), ep = gftt_epitch(R.w);
             for (int p = tid; p < n; p += kSelThreads) {
                 const int y = p / iw + 1, x = p - (y - 1) * iw + 1;
                 const float* Ec = Ep + (size_t)y * ep + x;
                 const float v = Ec[0] > thr ? Ec[0] : 0.f;
                 if (v == 0.f) continue;
+                if constexpr (masked) {
+                    if (Mp[(size_t)y * a.mask_pitch + x] == 0) continue;
+                }
                 float m = v;
 #pragma unroll
                 for (int dy = -1; dy <= 1; ++dy)
@@ -1189,8 +1257,14 @@ void gftt_plan(GfttArgs& a, int max_area)
 
 hipError_t launch_gftt_eig(const GfttArgs& a, hipStream_t s)
 {
-    if (a.compact) hipLaunchKernelGGL(gftt_eig_kernel<true>, dim3(a.ncblk), dim3(64 * kEigWaves), 0, s, a);
-    else hipLaunchKernelGGL(gftt_eig_kernel<false>, dim3(a.ncblk), dim3(64 * kEigWaves), 0, s, a);
+    const dim3 grid(a.ncblk), block(64 * kEigWaves);
+    if (a.mask) {
+        if (a.compact) hipLaunchKernelGGL(gftt_eig_masked_kernel<true>, grid, block, 0, s, a);
+        else hipLaunchKernelGGL(gftt_eig_masked_kernel<false>, grid, block, 0, s, a);
+    } else {
+        if (a.compact) hipLaunchKernelGGL(gftt_eig_kernel<true>, grid, block, 0, s, a);
+        else hipLaunchKernelGGL(gftt_eig_kernel<false>, grid, block, 0, s, a);
+    }
     return hipGetLastError();
 }
 
@@ -1217,7 +1291,9 @@ hipError_t launch_gftt_select(const GfttArgs& a, hipStream_t s)
     const unsigned long long bit = 1ull << (dev & 63);
     if (!(opted.load(std::memory_order_acquire) & bit)) {
         for (const void* k : {reinterpret_cast<const void*>(&gftt_select_kernel<2>),
-                              reinterpret_cast<const void*>(&gftt_select_kernel<6>)}) {
+                              reinterpret_cast<const void*>(&gftt_select_kernel<6>),
+                              reinterpret_cast<const void*>(&gftt_select_kernel<2, true>),
+                              reinterpret_cast<const void*>(&gftt_select_kernel<6, true>)}) {
             hipFuncAttributes fa;
             e = hipFuncGetAttributes(&fa, k);
             if (e != hipSuccess) return e;
@@ -1231,7 +1307,11 @@ hipError_t launch_gftt_select(const GfttArgs& a, hipStream_t s)
     const double md2 = a.min_distance * a.min_distance;
     int rad = (int)ceil(a.min_distance) - 1;
     if ((double)(rad + 1) * (rad + 1) < md2) rad++;
-    if (a.min_distance >= 1.0 && rad > 2)
+    const bool wide = a.min_distance >= 1.0 && rad > 2;
+    if (a.mask) {
+        if (wide) hipLaunchKernelGGL((gftt_select_kernel<6, true>), dim3(a.nroi), dim3(kSelThreads), smem, s, a);
+        else hipLaunchKernelGGL((gftt_select_kernel<2, true>), dim3(a.nroi), dim3(kSelThreads), smem, s, a);
+    } else if (wide)
         hipLaunchKernelGGL(gftt_select_kernel<6>, dim3(a.nroi), dim3(kSelThreads), smem, s, a);
     else
         hipLaunchKernelGGL(gftt_select_kernel<2>, dim3(a.nroi), dim3(kSelThreads), smem, s, a);

@@ -191,7 +191,11 @@ __global__ __launch_bounds__(64) void gftt_resp_colsum_kernel(GfttRespArgs a)
     }
 }
 
-// per strip: max key and the local-maximum ballots (gftt_eig_kernel's layout)
+// per strip: max key and the local-maximum ballots (gftt_eig_kernel's layout).
+// masked (GfttRespArgs::mask): the max over the strip's pixels whose mask byte
+// is non-zero, INT_MIN (below every float's key, so a negative Harris maximum of
+// another strip still wins) when it has none; the ballots do not depend on it
+template <bool masked>
 __global__ __launch_bounds__(64) void gftt_resp_lmax_kernel(GfttRespArgs a)
 {
     const int r = roi_of_strip(a.rois, a.nroi, blockIdx.x);
@@ -204,13 +208,17 @@ __global__ __launch_bounds__(64) void gftt_resp_lmax_kernel(GfttRespArgs a)
     const bool x_in = out_lane && gx >= 1 && gx <= R.w - 2;
     const int H = R.h;
     const float* E = a.eig + R.off + gx;
+    // an output lane holds its own column (gx == xc): the image byte's addressing
+    const uint8_t* M = masked ? a.mask + (size_t)R.y * a.mask_pitch + R.x + gx : nullptr;
     uint64_t* lm = a.lmax + R.moff + (size_t)strip * H;
     const bool has_lm = R.w >= 3 && H >= 3;
     int best = INT_MIN;
     float e1 = 0.f, e2 = 0.f;
     for (int y = 0; y < H; ++y) {
         const float e = E[(size_t)y * gftt_epitch(R.w)];
-        if (out_lane) best = rfkey(e) > best ? rfkey(e) : best;
+        bool cnt = out_lane;
+        if constexpr (masked) cnt = out_lane && M[(size_t)y * a.mask_pitch] != 0;
+        if (cnt) best = rfkey(e) > best ? rfkey(e) : best;
         const int yc = y - 1;
         if (has_lm && yc >= 1 && yc <= H - 2) {  // uniform
             float m = fmaxf(e2, e);
@@ -241,7 +249,8 @@ hipError_t launch_gftt_resp(const GfttRespArgs& a, int ncblk, int max_w, int max
     else
         hipLaunchKernelGGL(gftt_resp_rowsum_run_kernel, dim3((max_h + 63) / 64, a.nroi), dim3(64), 0, s, a);
     hipLaunchKernelGGL(gftt_resp_colsum_kernel, dim3((max_w + 63) / 64, a.nroi), dim3(64), 0, s, a);
-    hipLaunchKernelGGL(gftt_resp_lmax_kernel, dim3(ncblk), dim3(64), 0, s, a);
+    if (a.mask) hipLaunchKernelGGL(gftt_resp_lmax_kernel<true>, dim3(ncblk), dim3(64), 0, s, a);
+    else hipLaunchKernelGGL(gftt_resp_lmax_kernel<false>, dim3(ncblk), dim3(64), 0, s, a);
     return hipGetLastError();
 }
 

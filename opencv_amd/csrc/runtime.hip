@@ -820,8 +820,11 @@ int gftt_prepare(const tbdk_roi* rois, int nroi, int width, int height, const tb
 }
 
 static void gftt_resp_args(GfttRespArgs& ra, const GfttScratch& sc, const uint8_t* img, int pitch,
-                           const GfttRoi* d_rois, int nroi, int block, int harris, double hk)
+                           const GfttRoi* d_rois, int nroi, int block, int harris, double hk,
+                           const uint8_t* mask = nullptr, int mask_pitch = 0)
 {
+    ra.mask = mask;
+    ra.mask_pitch = mask_pitch;
     ra.img = img;
     ra.pitch = pitch;
     ra.rois = d_rois;
@@ -889,7 +892,7 @@ int gftt_reserve(GfttScratch& sc, int device, int max_rois, int64_t max_px)
 
 int gftt_launch(tbdk_ctx* ctx, GfttScratch& sc, const uint8_t* img, int pitch, const GfttRoi* d_rois,
                 const GfttPlan& plan, const tbdk_gftt_params* p, float* corners, int32_t* counts, hipStream_t s,
-                hipEvent_t after_eig, int corner_stride, const GfttRoi* h_rois)
+                hipEvent_t after_eig, int corner_stride, const GfttRoi* h_rois, const uint8_t* mask, int mask_pitch)
 {
     if (corner_stride != 0 && corner_stride < p->max_corners) return TBDK_EINVAL;
     int rc = gftt_reserve(sc, ctx->device, plan.nroi, plan.total);
@@ -897,6 +900,8 @@ int gftt_launch(tbdk_ctx* ctx, GfttScratch& sc, const uint8_t* img, int pitch, c
     DeviceGuard g(ctx->device);
     int rec = timing_begin(ctx, "gftt", s);
     GfttArgs a;
+    a.mask = mask;
+    a.mask_pitch = mask ? mask_pitch : 0;
     a.img = img;
     a.pitch = pitch;
     a.rois = d_rois;
@@ -933,7 +938,8 @@ int gftt_launch(tbdk_ctx* ctx, GfttScratch& sc, const uint8_t* img, int pitch, c
         rc = gftt_reserve_resp(sc, ctx->device, plan.total);
         if (rc != TBDK_OK) return rc;
         GfttRespArgs ra;
-        gftt_resp_args(ra, sc, img, pitch, d_rois, plan.nroi, p->block_size, p->use_harris, p->harris_k);
+        gftt_resp_args(ra, sc, img, pitch, d_rois, plan.nroi, p->block_size, p->use_harris, p->harris_k, a.mask,
+                       a.mask_pitch);
         e = launch_gftt_resp(ra, plan.ncblk, plan.max_w, plan.max_h, plan.max_area, s);
         if (e == hipSuccess && after_eig) e = hipEventRecord(after_eig, s);
         if (e == hipSuccess) e = launch_gftt_select(a, s);
@@ -955,7 +961,15 @@ int tbdk_gftt_reserve(tbdk_ctx* ctx, int max_rois, int64_t max_total_pixels)
 int tbdk_gftt_rois(tbdk_ctx* ctx, const uint8_t* img, int width, int height, int pitch, const tbdk_roi* rois,
                    int nroi, const tbdk_gftt_params* p, float* corners, int32_t* counts, void* stream)
 {
+    return tbdk_gftt_rois_masked(ctx, img, width, height, pitch, nullptr, 0, rois, nroi, p, corners, counts, stream);
+}
+
+int tbdk_gftt_rois_masked(tbdk_ctx* ctx, const uint8_t* img, int width, int height, int pitch, const uint8_t* mask,
+                          int mask_pitch, const tbdk_roi* rois, int nroi, const tbdk_gftt_params* p, float* corners,
+                          int32_t* counts, void* stream)
+{
     if (!ctx || !p || nroi < 0) return TBDK_EINVAL;
+    if (mask && mask_pitch < width) return TBDK_EINVAL;
     if (nroi == 0) return TBDK_OK;
     if (!img || !rois || !corners || !counts || width <= 0 || height <= 0 || pitch < width) return TBDK_EINVAL;
     GfttPlan plan;
@@ -970,7 +984,7 @@ int tbdk_gftt_rois(tbdk_ctx* ctx, const uint8_t* img, int width, int height, int
     hipError_t e = hipMemcpyAsync(ctx->gftt.rois, tab.data(), sizeof(GfttRoi) * (size_t)nroi, hipMemcpyHostToDevice, s);
     if (e != hipSuccess) return map_err(e);
     return gftt_launch(ctx, ctx->gftt, img, pitch, static_cast<const GfttRoi*>(ctx->gftt.rois), plan, p, corners,
-                       counts, s, nullptr, 0, tab.data());
+                       counts, s, nullptr, 0, tab.data(), mask, mask_pitch);
 }
 
 int tbdk_corner_min_eig_val(tbdk_ctx* ctx, const uint8_t* img, int width, int height, int pitch, float* dst,

@@ -345,6 +345,11 @@ struct tbdk_tbd {
     std::vector<int> det_order;                   // scratch: detections by left edge
     GfttScratch gftt;   // the early GFTT's (early_s); the loop's own, not the context's
     GfttScratch gftt2;  // the post-tracker GFTT's (side), so the next step's early GFTT need not wait for it
+    // tbdk_tbd_set_corner_mask: the caller's static mask plane (frame size), read
+    // by both GFTT launches; fixed once the first step has run (stepped)
+    const uint8_t* cmask = nullptr;
+    int cmask_pitch = 0;
+    bool stepped = false;
     hipEvent_t pyr_ready = nullptr;               // this step's pyramid built on the step's stream
     // zero-copy staging: the kernels read the pinned host tables (fit entries,
     // slot lists, GFTT ROI tables) and the fit kernel
@@ -797,7 +802,7 @@ int early_launch(tbdk_tbd* t, const tbdk_gftt_params& gp, const tbdk_roi* rois, 
     const int row0 = c.max_tracks * (1 + set) + tab0;
     rc = gftt_launch(t->ctx, t->gftt, img, ipitch, dtab, eplan, &gp,
                      reinterpret_cast<float*>(t->slot_pts + (size_t)row0 * kSlotPts), t->slot_counts + row0, es,
-                     nullptr, kSlotPts, htab);
+                     nullptr, kSlotPts, htab, t->cmask, t->cmask_pitch);
     if (rc != TBDK_OK) return rc;
     return map_status(hipEventRecord(t->early_done[set], es));
 }
@@ -929,6 +934,7 @@ int step_impl(tbdk_tbd* t, const uint8_t* frame, int pitch, int frame_id, const 
     if (!t || !frame || ndets < 0 || (ndets > 0 && !dets) || pitch < t->cfg.width ||
         (next && next_pitch < t->cfg.width))
         return TBDK_EINVAL;
+    t->stepped = true;
     using clk = std::chrono::steady_clock;
     const auto t_step0 = clk::now();
 #ifdef TBDK_STEP_PROFILE
@@ -1402,7 +1408,7 @@ int step_impl(tbdk_tbd* t, const uint8_t* frame, int pitch, int frame_id, const 
         const tbdk_level& L0 = P.lv[0];
         rc = gftt_launch(t->ctx, t->gftt2, L0.data + (size_t)L0.pad * L0.pitch + L0.pad, L0.pitch, t->d_tab, plan, &gp,
                          reinterpret_cast<float*>(t->slot_pts + (size_t)prow0 * kSlotPts), t->slot_counts + prow0,
-                         t->side, next ? t->eig_done : nullptr, kSlotPts, t->h_tab);
+                         t->side, next ? t->eig_done : nullptr, kSlotPts, t->h_tab, t->cmask, t->cmask_pitch);
         if (rc != TBDK_OK) return rc;
     }
     // post_done also after an early GFTT none of whose ROIs was used: the next
@@ -1508,6 +1514,14 @@ int tbdk_probe_step_profile(double* out, int cap)
     return TBDK_OK;
 }
 #endif
+
+int tbdk_tbd_set_corner_mask(tbdk_tbd* t, const uint8_t* mask, int mask_pitch)
+{
+    if (!t || t->stepped || (mask && mask_pitch < t->cfg.width)) return TBDK_EINVAL;
+    t->cmask = mask;
+    t->cmask_pitch = mask ? mask_pitch : 0;
+    return TBDK_OK;
+}
 
 int tbdk_tbd_step(tbdk_tbd* t, const uint8_t* frame, int pitch, int frame_id, const tbdk_detection* dets,
                   int ndets, tbdk_frame_metrics* metrics, void* stream)

@@ -382,6 +382,13 @@ struct GfttArgs {
     // kernel's binary search over them is a chain of host-link round trips
     int ninl;
     GfttRoiC inl[kGfttInline];
+    // optional corner mask (tbdk_gftt_rois_masked), a u8 plane of the image's
+    // size in its coordinates, rows mask_pitch bytes apart, any alignment: the
+    // ROI max is taken over the non-zero bytes only and only they can be
+    // corners.  nullptr: the unmasked kernel instances, which read neither field
+    // (last in the struct, so every other argument keeps its place)
+    const uint8_t* mask;
+    int mask_pitch;
 };
 constexpr int kGfttCap = 16384;  // candidates per ROI (LDS-resident for the sort)
 // scratch sizes for (rois, pixels): strips <= px/60 + rois; local-maximum words
@@ -408,7 +415,7 @@ void gftt_scratch_free(GfttScratch& sc);
 int gftt_launch(tbdk_ctx* ctx, GfttScratch& sc, const uint8_t* img, int pitch, const GfttRoi* d_rois, const GfttPlan& plan,
                 const tbdk_gftt_params* p, float* corners, int32_t* counts, hipStream_t s,
                 hipEvent_t after_eig = nullptr, int corner_stride = 0,  // 0: max_corners
-                const GfttRoi* h_rois = nullptr);
+                const GfttRoi* h_rois = nullptr, const uint8_t* mask = nullptr, int mask_pitch = 0);
 hipError_t launch_gftt(const GfttArgs& a, hipStream_t s, hipEvent_t after_eig = nullptr);
 hipError_t launch_gftt_eig(const GfttArgs& a, hipStream_t s);  // eigenvalue planes only
 hipError_t launch_gftt_select(const GfttArgs& a, hipStream_t s);
@@ -429,6 +436,8 @@ struct GfttRespArgs {
     float k, k2;     // Sobel taps x 1/(4*block*255)
     float kf;        // (float)harris_k (the SIMD paths)
     double hk;       // harris_k (the scalar path)
+    const uint8_t* mask;  // optional corner mask (GfttArgs::mask), read by the strip maxima only
+    int mask_pitch;
 };
 hipError_t launch_gftt_resp(const GfttRespArgs& a, int ncblk, int max_w, int max_h, int max_area, hipStream_t s);
 int gftt_reserve_resp(GfttScratch& sc, int device, int64_t max_px);

@@ -637,7 +637,9 @@ class GoodFeaturesToTrackDetector:
     """cv::cuda::createGoodFeaturesToTrackDetector(CV_8UC1, maxCorners, qualityLevel,
     minDistance, blockSize=3, useHarrisDetector=False, harrisK=0.04)
     (cudaimgproc.hpp:603-604) with the CPU goodFeaturesToTrack semantics, applied
-    to a batch of box ROIs of one image."""
+    to a batch of box ROIs of one image, optionally under an 8-bit mask
+    (goodFeaturesToTrack's `mask`: the quality threshold comes from the maximum
+    over the masked-in pixels, and only they can be corners)."""
 
     def __init__(self, maxCorners: int = 1000, qualityLevel: float = 0.01, minDistance: float = 0.0,
                  blockSize: int = 3, useHarrisDetector: bool = False, harrisK: float = 0.04, device: int = 0):
@@ -645,25 +647,38 @@ class GoodFeaturesToTrackDetector:
                                    1 if useHarrisDetector else 0, float(harrisK))
         self.ctx = Context.get(device)
 
-    def detect_rois(self, image: torch.Tensor, rois, stream=None):
+    def detect_rois(self, image: torch.Tensor, rois, stream=None, mask: torch.Tensor | None = None):
         """rois: iterable of (x, y, w, h).  Returns (corners (nroi, maxCorners, 2) f32,
-        counts (nroi,) i32) device tensors; corners are in image coordinates."""
+        counts (nroi,) i32) device tensors; corners are in image coordinates.
+        mask: optional 2-D uint8 device tensor of the image's shape with
+        stride(1) == 1 (any row stride: a slice of a larger tensor works); each
+        ROI reads its own rectangle of it (tbdk_gftt_rois_masked)."""
         if image.dtype != torch.uint8 or image.dim() != 2 or not image.is_cuda or image.stride(1) != 1:
             raise _lib.TbdkError("detect expects a 2-D uint8 device tensor")
+        if mask is not None and (not isinstance(mask, torch.Tensor) or mask.dtype != torch.uint8 or mask.dim() != 2 or
+                                 mask.device != image.device or mask.shape != image.shape or mask.stride(1) != 1):
+            raise _lib.TbdkError("mask must be a 2-D uint8 tensor of the image's shape on its device, stride(1) == 1")
         rois = list(rois)
         n = len(rois)
         arr = (_lib.Roi * max(n, 1))(*[_lib.Roi(int(x), int(y), int(w), int(h)) for (x, y, w, h) in rois])
         corners = torch.zeros((n, self.prm.max_corners, 2), dtype=torch.float32, device=image.device)
         counts = torch.zeros((n,), dtype=torch.int32, device=image.device)
-        _lib.check(self.ctx.lib.tbdk_gftt_rois(self.ctx.handle, C.c_void_p(image.data_ptr()), image.shape[1],
-                                               image.shape[0], image.stride(0), arr, n, C.byref(self.prm),
-                                               C.c_void_p(corners.data_ptr()), C.c_void_p(counts.data_ptr()),
-                                               _stream_ptr(stream)), "tbdk_gftt_rois")
+        if mask is None:
+            _lib.check(self.ctx.lib.tbdk_gftt_rois(self.ctx.handle, C.c_void_p(image.data_ptr()), image.shape[1],
+                                                   image.shape[0], image.stride(0), arr, n, C.byref(self.prm),
+                                                   C.c_void_p(corners.data_ptr()), C.c_void_p(counts.data_ptr()),
+                                                   _stream_ptr(stream)), "tbdk_gftt_rois")
+        else:
+            _lib.check(self.ctx.lib.tbdk_gftt_rois_masked(
+                self.ctx.handle, C.c_void_p(image.data_ptr()), image.shape[1], image.shape[0], image.stride(0),
+                C.c_void_p(mask.data_ptr()), int(mask.stride(0)), arr, n, C.byref(self.prm),
+                C.c_void_p(corners.data_ptr()), C.c_void_p(counts.data_ptr()), _stream_ptr(stream)),
+                "tbdk_gftt_rois_masked")
         return corners, counts
 
-    def detect(self, image: torch.Tensor, stream=None) -> torch.Tensor:
-        """Whole image as one ROI -> (K, 2) corners (CornersDetector::detect without mask)."""
-        c, n = self.detect_rois(image, [(0, 0, image.shape[1], image.shape[0])], stream)
+    def detect(self, image: torch.Tensor, stream=None, mask: torch.Tensor | None = None) -> torch.Tensor:
+        """Whole image as one ROI -> (K, 2) corners (CornersDetector::detect, with its mask)."""
+        c, n = self.detect_rois(image, [(0, 0, image.shape[1], image.shape[0])], stream, mask)
         k = int(n[0].item())
         if k < 0:
             raise _lib.TbdkError("candidate buffer overflow (image too large for one ROI)")

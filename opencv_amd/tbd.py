@@ -56,6 +56,24 @@ class TbdLoop:
         _lib.check(self.ctx.lib.tbdk_tbd_create(self.ctx.handle, C.byref(cfg), C.byref(h)), "tbdk_tbd_create")
         self.handle = h
         self._dets = (_lib.Detection * 4096)()
+        self._corner_mask = None
+
+    def set_corner_mask(self, mask: torch.Tensor | None):
+        """A static corner mask for the loop's GFTT (tbdk_tbd_set_corner_mask):
+        a 2-D uint8 device tensor of the frame's shape with stride(1) == 1, or
+        None to clear it.  Only before the first step.  The loop keeps a
+        reference; the caller must not change the tensor while the loop lives."""
+        if mask is None:
+            _lib.check(self.ctx.lib.tbdk_tbd_set_corner_mask(self.handle, None, 0), "tbdk_tbd_set_corner_mask")
+            self._corner_mask = None
+            return
+        if not isinstance(mask, torch.Tensor) or mask.dtype != torch.uint8 or mask.dim() != 2 or not mask.is_cuda or \
+                mask.device.index != self.ctx.device or mask.stride(1) != 1 or \
+                tuple(mask.shape) != (self.cfg.height, self.cfg.width):
+            raise _lib.TbdkError("corner mask must be a 2-D uint8 device tensor of the loop's frame size")
+        _lib.check(self.ctx.lib.tbdk_tbd_set_corner_mask(self.handle, C.c_void_p(mask.data_ptr()),
+                                                         int(mask.stride(0))), "tbdk_tbd_set_corner_mask")
+        self._corner_mask = mask
 
     @staticmethod
     def _check_frame(frame):

@@ -2,6 +2,7 @@
 """Records the real reference (buildOpticalFlowPyramid, calcOpticalFlowPyrLK,
 goodFeaturesToTrack, cornerMinEigenVal / cornerHarris, warpAffine,
 calcOpticalFlowFarneback, HOGDescriptor) on the cases of tests/_reference_cases.py
+(goodFeaturesToTrack under a mask: tests/_gftt_mask_cases.py)
 into tests/golden/reference_<op>.npz, through tools/reference_driver.cpp (how to
 build it: tools/record_reference_cases.md).
 
@@ -34,11 +35,13 @@ ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 sys.path.insert(0, os.path.join(ROOT, "tests"))
 import _oracle as O  # noqa: E402
 import _reference_cases as RC  # noqa: E402
+import _gftt_mask_cases as MC  # noqa: E402
 
 LIMIT = 256 * 1024
 STATES = ("default", "noavx2")
 # the state each oracle file models where the two differ (README, numerics)
-MODELLED = {"pyramid": "both", "pyrlk": "both", "warpaffine": "both", "gftt": "noavx2", "cornermaps": "noavx2",
+MODELLED = {"pyramid": "both", "pyrlk": "both", "warpaffine": "both", "gftt": "noavx2", "gftt_mask": "noavx2",
+            "cornermaps": "noavx2",
             "farneback": "noavx2", "farneback_box": "noavx2", "hog": "default"}
 
 
@@ -155,6 +158,26 @@ def rec_gftt(d):
         cases.append((dict(c=c.astype(np.uint16)), {}))
         meta.append((r, maxc, block, harris))
     return cases, dict(meta=np.array(meta, np.int32))
+
+
+def rec_gftt_mask(d):
+    """goodFeaturesToTrack with its mask argument (tests/_gftt_mask_cases.py); the
+    masks travel in the fixture, bit-packed"""
+    entries = MC.masks()
+    masks = [MC.mask_of(e) for e in entries]
+    extra = {}
+    for m, mask in enumerate(masks):
+        extra[f"mask_{m}_bits"], extra[f"mask_{m}_val"] = MC.pack_mask(mask)
+    cases = []
+    for r, m, maxc, ql, md, block, harris in MC.cases():
+        roi = MC.roi_image(r)
+        _, rd = d.run("gftt", dict(a=roi, mask=masks[m]), **img_kw(roi), maxc=maxc, ql=ql, md=md, block=block,
+                      harris=harris, k=MC.HARRIS_K)
+        c = rd("c", np.float32).reshape(-1, 2)
+        assert np.array_equal(c, c.astype(np.uint16))
+        cases.append((dict(c=c.astype(np.uint16)), {}))
+    extra["case_mask"] = np.array([c[1] for c in MC.cases()], np.int32)
+    return cases, extra
 
 
 def rec_cornermaps(d):
@@ -298,12 +321,14 @@ def merge(op, rec, whole_limit):
     return arrays, (state, ints_eq, share, maxabs)
 
 
-RECORDERS = {"pyramid": rec_pyramid, "pyrlk": rec_pyrlk, "gftt": rec_gftt, "cornermaps": rec_cornermaps,
+RECORDERS = {"pyramid": rec_pyramid, "pyrlk": rec_pyrlk, "gftt": rec_gftt, "gftt_mask": rec_gftt_mask,
+             "cornermaps": rec_cornermaps,
              "warpaffine": rec_warpaffine, "farneback": rec_farneback, "farneback_box": rec_farneback_box,
              "hog": rec_hog}
 # bytes up to which an output is stored whole (tests/_reference_cases.py: WHOLE_LIMIT).  The kernels are
 # compared with the box Farneback flows within a tolerance, so all six stay whole (about 7 KB under LIMIT)
-WHOLE = {"farneback": 20480, "farneback_box": 72800, "pyrlk": 1 << 20, "gftt": 1 << 20, "hog": 16384}
+WHOLE = {"farneback": 20480, "farneback_box": 72800, "pyrlk": 1 << 20, "gftt": 1 << 20, "gftt_mask": 1 << 20,
+         "hog": 16384}
 
 
 def save(path, arrays):
@@ -323,6 +348,9 @@ def case_label(op, i):
     if op == "gftt":
         r, maxc, ql, md, block, harris = RC.gftt_cases()[i]
         return f"roi {r} ({maxc}, {ql}, {md}) block {block}" + (" harris" if harris else "")
+    if op == "gftt_mask":
+        r, m, maxc, ql, md, block, harris = MC.cases()[i]
+        return f"roi {r} mask {MC.masks()[m][1]} ({maxc}, {ql}, {md}) block {block}" + (" harris" if harris else "")
     if op == "cornermaps":
         w, h, _ = RC.CMAP_SHAPES[i // len(RC.CMAP_MODES)]
         block, harris = RC.CMAP_MODES[i % len(RC.CMAP_MODES)]

@@ -12,7 +12,8 @@
 //   pyr   a= w= h= cn= winw= winh= maxl=           -> L<i> (u8), D<i> (i16, 2cn per pixel); prints the level sizes
 //   lk    a= b= w= h= cn= winw= winh= maxl= flags= pts= n= [init=] err=0|1
 //                                                  -> q (f32 pairs), st (u8), err (f32, if err=1)
-//   gftt  a= w= h= maxc= ql= md= block= harris= k= -> c (f32 pairs); prints the count
+//   gftt  a= w= h= maxc= ql= md= block= harris= k= [mask=] -> c (f32 pairs); prints the count
+//                                                  (mask: raw u8, w x h, goodFeaturesToTrack's mask)
 //   cmap  a= w= h= block= harris= k=               -> e (f32): cornerMinEigenVal / cornerHarris, ksize 3
 //   warp  a= w= h= m= (6 doubles, raw) dst= dw= dh= flags= border= bval=   -> w (u8)
 //   fb    a= b= w= h= ps= lv= ws= it= pn= sg= flags= [init=]               -> f (f32 pairs)
@@ -106,8 +107,12 @@ static int run(const std::string& op, const std::string& out)
         if (iarg("err")) wr(out, "err", err.data(), sizeof(float) * n);
     } else if (op == "gftt") {
         std::vector<Point2f> c;
-        goodFeaturesToTrack(a, c, iarg("maxc"), darg("ql"), darg("md"), noArray(), iarg("block"), iarg("harris") != 0,
-                            darg("k"));
+        if (has("mask"))
+            goodFeaturesToTrack(a, c, iarg("maxc"), darg("ql"), darg("md"), image("mask", w, h, 1), iarg("block"),
+                                iarg("harris") != 0, darg("k"));
+        else
+            goodFeaturesToTrack(a, c, iarg("maxc"), darg("ql"), darg("md"), noArray(), iarg("block"),
+                                iarg("harris") != 0, darg("k"));
         std::printf("corners %d\n", (int)c.size());
         wr(out, "c", c.data(), sizeof(Point2f) * c.size());
     } else if (op == "cmap") {
