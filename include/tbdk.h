@@ -517,6 +517,44 @@ int tbdk_corner_response(tbdk_ctx* ctx, const uint8_t* img, int width, int heigh
                          int dst_pitch, int block_size, int harris, double harris_k, void* stream);
 int tbdk_gftt_reserve(tbdk_ctx* ctx, int max_rois, int64_t max_total_pixels);
 
+/* GFTT and the corner response maps on 8U, 16U and 32F one-channel images.
+ * cornerEigenValsVecs takes CV_8UC1 or CV_32FC1 (imgproc/src/corner.cpp:258), and
+ * with it goodFeaturesToTrack, cornerMinEigenVal, cornerHarris and the
+ * cv::cuda::create*Corner / createGoodFeaturesToTrackDetector(srcType, ...)
+ * factories.  pix selects the pixel type of img: */
+#define TBDK_PIX_U8  0
+#define TBDK_PIX_U16 1
+#define TBDK_PIX_F32 2
+/* TBDK_PIX_U8 : tbdk_gftt_rois / tbdk_gftt_rois_masked / tbdk_corner_response
+ *               themselves (identical outputs).
+ * TBDK_PIX_F32: the reference's CV_32F path: the Sobel scale is
+ *               1 / (4 * blockSize) (the x 255 of the 8-bit path is not applied)
+ *               and the ksize-3 row filter is the float one (Dx row
+ *               S[x+1] - S[x-1]; Dy row S[x]*k0 + (S[x-1] + S[x+1])*k1, unfused);
+ *               everything from the column pass on is as for 8-bit images.
+ * TBDK_PIX_U16: an extension (the reference rejects CV_16U): exactly the
+ *               TBDK_PIX_F32 result on the image converted to float (the
+ *               conversion is exact and happens in the kernels' loads).
+ * pitch is in bytes.  Pixels must be finite: results equal the reference's
+ * wherever the reference's own intermediates stay finite; NaN and Inf pixels,
+ * and images whose covariances overflow, give unspecified values (never a
+ * fault or a hang).  On float data with a wide exponent range the eigenvalue
+ * walk's row segments rarely start on the reference's running sum; they are
+ * then walked again in the reference's order, so the result stays exact and
+ * the call takes up to a few times longer.
+ * mask NULL: unmasked.  Scratch, counts == -1 on candidate overflow, the
+ * "gftt_compact" / "gftt_eig_redo" options and the timing names are those of
+ * the 8-bit entries.
+ * TBDK_EINVAL: an unknown pix; an F32 img pointer or pitch that is not a
+ * multiple of 4; a U16 one that is not a multiple of 2; pitch below a row's
+ * bytes; whatever the 8-bit entries reject. */
+int tbdk_gftt_rois_px(tbdk_ctx* ctx, const void* img, int pix, int width, int height, int pitch,
+                      const uint8_t* mask, int mask_pitch,
+                      const tbdk_roi* rois, int nroi, const tbdk_gftt_params* params,
+                      float* corners, int32_t* counts, void* stream);
+int tbdk_corner_response_px(tbdk_ctx* ctx, const void* img, int pix, int width, int height, int pitch,
+                            float* dst, int dst_pitch, int block_size, int harris, double harris_k, void* stream);
+
 /* ---- KLT box propagation ----------------------------------------------------- */
 
 /* Result of fitting one box's tracked corners (prev -> next). */

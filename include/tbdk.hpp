@@ -364,10 +364,13 @@ private:
     std::unique_ptr<Pyramid> pyr_[2];
 };
 
-// cv::cuda::CornersDetector from createGoodFeaturesToTrackDetector(CV_8UC1,
+// cv::cuda::CornersDetector from createGoodFeaturesToTrackDetector(srcType,
 // maxCorners, qualityLevel, minDistance, blockSize=3, useHarris=false, harrisK=0.04)
 // (cudaimgproc.hpp:582,603-604).  detect() runs on the whole image; detectRois()
 // is the batched per-box form the TBD loop uses (one launch set for all boxes).
+// A GpuImage is CV_8UC1; a GpuMatView carries its depth: DEPTH_8U, DEPTH_32F
+// (CV_32FC1, finite pixels) or DEPTH_16U (the 32F result of the same values),
+// one channel (tbdk_gftt_rois_px); any other view throws Error(TBDK_EINVAL).
 class CornersDetector {
 public:
     static std::unique_ptr<CornersDetector> create(Context& ctx, int maxCorners = 1000, double qualityLevel = 0.01,
@@ -416,6 +419,44 @@ public:
               "tbdk_gftt_rois_masked");
     }
 
+    // ... on a typed view (8U, 16U or 32F, one channel), without and with a mask
+    void detect(const GpuMatView& image, float* corners, int32_t* count, void* stream = nullptr)
+    {
+        tbdk_roi r{0, 0, image.width, image.height};
+        detectRois(image, &r, 1, corners, count, stream);
+    }
+    void detect(const GpuMatView& image, const GpuImage& mask, float* corners, int32_t* count, void* stream = nullptr)
+    {
+        tbdk_roi r{0, 0, image.width, image.height};
+        detectRois(image, mask, &r, 1, corners, count, stream);
+    }
+    void detectRois(const GpuMatView& image, const tbdk_roi* rois, int nroi, float* corners, int32_t* counts,
+                    void* stream = nullptr)
+    {
+        check(tbdk_gftt_rois_px(ctx_->get(), image.data, pixOf(image, "CornersDetector: image type"), image.width,
+                                image.height, image.pitch, nullptr, 0, rois, nroi, &p_, corners, counts, stream),
+              "tbdk_gftt_rois_px");
+    }
+    void detectRois(const GpuMatView& image, const GpuImage& mask, const tbdk_roi* rois, int nroi, float* corners,
+                    int32_t* counts, void* stream = nullptr)
+    {
+        if (!mask.data || mask.width != image.width || mask.height != image.height)
+            throw Error(TBDK_EINVAL, "CornersDetector: mask size");
+        check(tbdk_gftt_rois_px(ctx_->get(), image.data, pixOf(image, "CornersDetector: image type"), image.width,
+                                image.height, image.pitch, mask.data, mask.pitch, rois, nroi, &p_, corners, counts,
+                                stream),
+              "tbdk_gftt_rois_px");
+    }
+
+    // TBDK_PIX_* of a one-channel 8U / 16U / 32F view
+    static int pixOf(const GpuMatView& v, const char* what)
+    {
+        if (v.cn == 1 && v.depth == DEPTH_8U) return TBDK_PIX_U8;
+        if (v.cn == 1 && v.depth == DEPTH_16U) return TBDK_PIX_U16;
+        if (v.cn == 1 && v.depth == DEPTH_32F) return TBDK_PIX_F32;
+        throw Error(TBDK_EINVAL, what);
+    }
+
 private:
     CornersDetector(Context& ctx, int maxc, double q, double md, int block, bool harris, double k) : ctx_(&ctx)
     {
@@ -439,6 +480,17 @@ inline void cornerResponse(Context& ctx, const GpuImage& src, float* dst, int ds
     check(tbdk_corner_response(ctx.get(), src.data, src.width, src.height, src.pitch, dst, dst_pitch, blockSize,
                                harris ? 1 : 0, k, stream),
           "tbdk_corner_response");
+}
+
+// ... of a typed view: createMinEigenValCorner / createHarrisCorner(CV_8UC1 or CV_32FC1, ...),
+// and 16U as the 32F result of the same values (tbdk_corner_response_px)
+inline void cornerResponse(Context& ctx, const GpuMatView& src, float* dst, int dst_pitch, int blockSize = 3,
+                           bool harris = false, double k = 0.04, void* stream = nullptr)
+{
+    check(tbdk_corner_response_px(ctx.get(), src.data, CornersDetector::pixOf(src, "cornerResponse: image type"),
+                                  src.width, src.height, src.pitch, dst, dst_pitch, blockSize, harris ? 1 : 0, k,
+                                  stream),
+          "tbdk_corner_response_px");
 }
 
 // cv::cuda::pyrDown (cudawarping.hpp:201): dst must be ((w+1)/2, (h+1)/2)

@@ -18,6 +18,7 @@ TBDK_EHIP = -2
 TBDK_ENOMEM = -3
 TBDK_ENODEV = -4
 TBDK_MAX_LEVELS = 8
+TBDK_PIX_U8, TBDK_PIX_U16, TBDK_PIX_F32 = 0, 1, 2  # include/tbdk.h: pixel types of the *_px entries
 TBDK_ABI_VERSION = 2  # include/tbdk.h: the struct layouts below
 OPTFLOW_USE_INITIAL_FLOW = 4
 OPTFLOW_LK_GET_MIN_EIGENVALS = 8
@@ -253,6 +254,11 @@ SIGNATURES = {
                                         C.POINTER(Roi), C.c_int, C.POINTER(GfttParams), C.c_void_p, C.c_void_p,
                                         C.c_void_p]),
     "tbdk_gftt_reserve": (C.c_int, [C.c_void_p, C.c_int, C.c_int64]),
+    "tbdk_gftt_rois_px": (C.c_int, [C.c_void_p, C.c_void_p, C.c_int, C.c_int, C.c_int, C.c_int, C.c_void_p, C.c_int,
+                                    C.POINTER(Roi), C.c_int, C.POINTER(GfttParams), C.c_void_p, C.c_void_p,
+                                    C.c_void_p]),
+    "tbdk_corner_response_px": (C.c_int, [C.c_void_p, C.c_void_p, C.c_int, C.c_int, C.c_int, C.c_int, C.c_void_p,
+                                          C.c_int, C.c_int, C.c_int, C.c_double, C.c_void_p]),
     "tbdk_box_propagate": (C.c_int, [C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_int,
                                      C.c_int, C.c_void_p, C.c_void_p]),
     "tbdk_ransac_default_params": (C.c_int, [C.POINTER(RansacParams)]),

@@ -28,6 +28,11 @@
 // max is taken over the masked-in pixels and gftt_select admits only masked-in
 // candidates; these are kernel instances of their own (gftt_eig_masked_kernel,
 // gftt_select_kernel<R, true>), the unmasked ones never read the mask.
+// 16U and 32F images (tbdk_gftt_rois_px; cornerEigenValsVecs' CV_32FC1 path, a
+// 16U image being the 32F image of the same values) run the same walk from
+// kernels of their own again (gftt_eigpx_kernel<compact, masked, pix>): only the
+// lane's load and the Sobel row terms differ.  On float data the fresh-start
+// verification below fails routinely, and the re-walk carries the exactness.
 #include <atomic>
 #include <cfloat>
 #include <cmath>
@@ -109,6 +114,14 @@ __device__ __forceinline__ SobelRow sobel_row(float s0, float s1, float s2, floa
     u = u + k * s2;
     return SobelRow{t, u};
 }
+// ... of a 32F image (TBDK_PIX_F32; a 16U image is one converted in the load):
+// the reference's float row filter for ksize 3, SymmRowSmallFilter<float, float>
+// (filter.simd.hpp:1708-1743, 2425-2469) in its unfused form: rx = S[x+1] - S[x-1],
+// ry = S[x]*k0 + (S[x-1] + S[x+1])*k1
+__device__ __forceinline__ SobelRow sobel_row_f32(float s0, float s1, float s2, float k, float k2)
+{
+    return SobelRow{s2 - s0, s1 * k2 + (s0 + s2) * k};
+}
 
 // Fused Sobel -> cov -> boxFilter -> min eigenvalue for one 56-column strip of
 // a ROI per workgroup.  Lane L holds ROI column x0 - 4 + L (lanes 4..59 produce
@@ -171,9 +184,17 @@ __device__ __forceinline__ bool eig_mask_ld(const EigMask& m, int row)
     return __builtin_amdgcn_raw_buffer_load_b8(m.rs, m.col, row * m.pitch, 0) != 0;
 }
 
+// PX: the image's pixel type (TBDK_PIX_*); the lane's one load of a row is of
+// the pixel's size, g.pitch in bytes
+template <int PX = TBDK_PIX_U8>
 __device__ __forceinline__ float eig_ld(const EigLane& g, int row)
 {
-    return (float)__builtin_amdgcn_raw_buffer_load_b8(g.rs, g.x, row * g.pitch, 0);
+    if constexpr (PX == TBDK_PIX_F32)
+        return __uint_as_float(__builtin_amdgcn_raw_buffer_load_b32(g.rs, g.x * 4, row * g.pitch, 0));
+    else if constexpr (PX == TBDK_PIX_U16)
+        return (float)__builtin_amdgcn_raw_buffer_load_b16(g.rs, g.x * 2, row * g.pitch, 0);
+    else
+        return (float)__builtin_amdgcn_raw_buffer_load_b8(g.rs, g.x, row * g.pitch, 0);
 }
 
 // Sobel row terms of the pixel row whose own value is v (neighbours by DPP).
@@ -183,10 +204,12 @@ __device__ __forceinline__ float eig_ld(const EigLane& g, int row)
 // column's neighbours in the opposite order and swaps them, and then holds that
 // column's Sobel terms and covariances exactly — the box filter's reflect-101
 // of the cov image (cov(-1) = cov(1)) with no per-channel fix-up.
+template <int PX = TBDK_PIX_U8>
 __device__ __forceinline__ SobelRow eig_srow(const EigLane& g, float v)
 {
     const float l = from_left(v), rr = from_right(v);
-    return sobel_row(g.mir ? rr : l, v, g.mir ? l : rr, g.k, g.k2);
+    if constexpr (PX != TBDK_PIX_U8) return sobel_row_f32(g.mir ? rr : l, v, g.mir ? l : rr, g.k, g.k2);
+    else return sobel_row(g.mir ? rr : l, v, g.mir ? l : rr, g.k, g.k2);
 }
 
 // the three cov channels of one row and their boxFilter row sums ((l + c) + r in double)
@@ -217,24 +240,24 @@ __device__ __forceinline__ void eig_rowsums(const EigLane& g, const SobelRow& p,
 // masked: best is the max over the own pixels whose mask byte is non-zero (it
 // stays INT_MIN, below every float's key, when the segment has none); the
 // eigenvalues, ballots and compact values do not depend on the mask.
-template <bool compact, bool masked, int PREF = compact ? TBDK_GFTT_EIG_PREF_C : kEigPref>
+template <bool compact, bool masked, int PREF = compact ? TBDK_GFTT_EIG_PREF_C : kEigPref, int PX = TBDK_PIX_U8>
 __device__ __forceinline__ void eig_segment(const EigLane& g, const EigMask& gm, float* __restrict__ E,
                                             uint64_t* __restrict__ lm,
                                             int w, int ep, int y0, int y1, int ys, int ye, int ycap, bool fresh,
                                             double (&S)[3], double (&S0)[3], double (&Scap)[3], int& best, int ccol)
 {
     const int H = g.H;
-    auto pix = [&](int yy) { return eig_ld(g, refl(yy, H)); };
-    auto pix_fwd = [&](int yy) { return eig_ld(g, yy < H ? yy : g.hm2); };  // yy in [0, H]
+    auto pix = [&](int yy) { return eig_ld<PX>(g, refl(yy, H)); };
+    auto pix_fwd = [&](int yy) { return eig_ld<PX>(g, yy < H ? yy : g.hm2); };  // yy in [0, H]
     const int lane = threadIdx.x & 63;
     const bool x_in = g.out_lane && g.x >= 1 && g.x <= w - 2;
     double qa[3], qb[3];  // rs(y - 1), rs(y)
     {
         const int rm = refl(ys - 1, H);  // the box filter reflects cov rows
-        eig_rowsums(g, eig_srow(g, pix(rm - 1)), eig_srow(g, pix(rm)), eig_srow(g, pix(rm + 1)), qa);
+        eig_rowsums(g, eig_srow<PX>(g, pix(rm - 1)), eig_srow<PX>(g, pix(rm)), eig_srow<PX>(g, pix(rm + 1)), qa);
     }
-    SobelRow wa = eig_srow(g, pix(ys)), wb = eig_srow(g, pix(ys + 1));
-    eig_rowsums(g, eig_srow(g, pix(ys - 1)), wa, wb, qb);
+    SobelRow wa = eig_srow<PX>(g, pix(ys)), wb = eig_srow<PX>(g, pix(ys + 1));
+    eig_rowsums(g, eig_srow<PX>(g, pix(ys - 1)), wa, wb, qb);
     if (fresh) {
 #pragma unroll
         for (int ch = 0; ch < 3; ++ch) S[ch] = (0.0 + qa[ch]) + qb[ch];
@@ -261,7 +284,7 @@ __device__ __forceinline__ void eig_segment(const EigLane& g, const EigMask& gm,
         double in[3];
         SobelRow wc = wb;
         if (ST || has_next) {  // entering cov row y + 1 (image rows y, y+1, y+2)
-            wc = eig_srow(g, cur);
+            wc = eig_srow<PX>(g, cur);
             eig_rowsums(g, wa, wb, wc, in);
         } else {  // rs(refl(H)) == rs(H - 2) == rs(y - 1)
 #pragma unroll
@@ -344,9 +367,11 @@ __device__ __forceinline__ void eig_segment(const EigLane& g, const EigMask& gm,
 
 // compact (GfttArgs::compact, see eig_segment): one instantiation per mode,
 // so each has its own register budget
-template <bool compact, bool masked>
+template <bool compact, bool masked, int PX = TBDK_PIX_U8>
 __device__ __forceinline__ void gftt_eig_body(const GfttArgs& a)
 {
+    constexpr int kPref = compact ? TBDK_GFTT_EIG_PREF_C : kEigPref;
+    constexpr int kBpp = PX == TBDK_PIX_F32 ? 4 : PX == TBDK_PIX_U16 ? 2 : 1;  // bytes per pixel
     __shared__ double s_cap[kEigWaves][3][64];
     __shared__ double s_drift[3][64];
     __shared__ int s_best[kEigWaves];
@@ -379,14 +404,18 @@ __device__ __forceinline__ void gftt_eig_body(const GfttArgs& a)
         g.x = xm;
         g.mir = xc < 0 || xc >= w;
     }
-    const double scale = 1.0 / ((double)(1 << 2) * 3 * 255.0);
+    // cornerEigenValsVecs' scale: the x 255 is the 8-bit image's only (corner.cpp:250-256)
+    const double scale = PX == TBDK_PIX_U8 ? 1.0 / ((double)(1 << 2) * 3 * 255.0) : 1.0 / ((double)(1 << 2) * 3);
     g.k = (float)(1.0 * scale);
     g.k2 = (float)(2.0 * scale);
     g.H = H;
     g.hm2 = H >= 2 ? H - 2 : 0;
     g.pitch = a.pitch;
-    g.rs = __builtin_amdgcn_make_buffer_rsrc(const_cast<uint8_t*>(a.img + (size_t)R.y * a.pitch + R.x), (short)0,
-                                             a.pitch * H, 0x00020000);
+    // the ROI's rows as one buffer (every lane loads a column inside the ROI);
+    // for the wider pixels its last row ends with the ROI's
+    g.rs = __builtin_amdgcn_make_buffer_rsrc(const_cast<uint8_t*>(a.img + (size_t)R.y * a.pitch + (size_t)R.x * kBpp),
+                                             (short)0, PX == TBDK_PIX_U8 ? a.pitch * H : a.pitch * (H - 1) + R.w * kBpp,
+                                             0x00020000);
     EigMask gm{};
     if constexpr (masked) {  // rows a.mask_pitch apart; the last row ends with the ROI
         gm.rs = __builtin_amdgcn_make_buffer_rsrc(const_cast<uint8_t*>(a.mask + (size_t)R.y * a.mask_pitch + R.x),
@@ -426,8 +455,8 @@ __device__ __forceinline__ void gftt_eig_body(const GfttArgs& a)
     };
     GFTT_ESTAMP(0);
     if (live) {
-        eig_segment<compact, masked>(g, gm, E, has_lm ? lm : nullptr, R.w, gftt_epitch(R.w), y0, y1, ys, ye, ycap,
-                                     true, S, S0, Scap, best, ccol);
+        eig_segment<compact, masked, kPref, PX>(g, gm, E, has_lm ? lm : nullptr, R.w, gftt_epitch(R.w), y0, y1, ys, ye,
+                                                ycap, true, S, S0, Scap, best, ccol);
         if (ycap >= 0) {
 #pragma unroll
             for (int ch = 0; ch < 3; ++ch) s_cap[wv][ch][lane] = Scap[ch];
@@ -455,8 +484,8 @@ __device__ __forceinline__ void gftt_eig_body(const GfttArgs& a)
         __syncthreads();  // s_cap is rewritten below
         if (wv >= bad && live) {
             best = INT_MIN;
-            eig_segment<compact, masked>(g, gm, E, has_lm ? lm : nullptr, R.w, gftt_epitch(R.w), y0, y1, ys, ye, ycap,
-                                         false, S, S0, Scap, best, ccol);
+            eig_segment<compact, masked, kPref, PX>(g, gm, E, has_lm ? lm : nullptr, R.w, gftt_epitch(R.w), y0, y1, ys,
+                                                    ye, ycap, false, S, S0, Scap, best, ccol);
             if (ycap >= 0) {
 #pragma unroll
                 for (int ch = 0; ch < 3; ++ch) s_cap[wv][ch][lane] = Scap[ch];
@@ -493,6 +522,15 @@ template <bool compact>
 __global__ __launch_bounds__(64 * kEigWaves) void gftt_eig_masked_kernel(GfttArgs a)
 {
     gftt_eig_body<compact, true>(a);
+}
+
+// 16U and 32F images (tbdk_gftt_rois_px): kernels of their own name again;
+// only the lane's load and the Sobel row terms differ (eig_ld, eig_srow)
+template <bool compact, bool masked, int PX>
+__global__ __launch_bounds__(64 * kEigWaves) void gftt_eigpx_kernel(GfttArgs a)
+{
+    static_assert(PX == TBDK_PIX_U16 || PX == TBDK_PIX_F32, "the 8-bit kernels are gftt_eig_kernel / gftt_eig_masked_kernel");
+    gftt_eig_body<compact, masked, PX>(a);
 }
 
 // Candidate sort key: the reference order (value desc, then address desc,
@@ -1255,10 +1293,26 @@ void gftt_plan(GfttArgs& a, int max_area)
     a.img_bytes = (int)img;
 }
 
-hipError_t launch_gftt_eig(const GfttArgs& a, hipStream_t s)
+template <int PX>
+static void launch_gftt_eigpx(const GfttArgs& a, dim3 grid, dim3 block, hipStream_t s)
+{
+    if (a.mask) {
+        if (a.compact) hipLaunchKernelGGL((gftt_eigpx_kernel<true, true, PX>), grid, block, 0, s, a);
+        else hipLaunchKernelGGL((gftt_eigpx_kernel<false, true, PX>), grid, block, 0, s, a);
+    } else {
+        if (a.compact) hipLaunchKernelGGL((gftt_eigpx_kernel<true, false, PX>), grid, block, 0, s, a);
+        else hipLaunchKernelGGL((gftt_eigpx_kernel<false, false, PX>), grid, block, 0, s, a);
+    }
+}
+
+hipError_t launch_gftt_eig(const GfttArgs& a, hipStream_t s, int pix)
 {
     const dim3 grid(a.ncblk), block(64 * kEigWaves);
-    if (a.mask) {
+    if (pix == TBDK_PIX_F32) {
+        launch_gftt_eigpx<TBDK_PIX_F32>(a, grid, block, s);
+    } else if (pix == TBDK_PIX_U16) {
+        launch_gftt_eigpx<TBDK_PIX_U16>(a, grid, block, s);
+    } else if (a.mask) {
         if (a.compact) hipLaunchKernelGGL(gftt_eig_masked_kernel<true>, grid, block, 0, s, a);
         else hipLaunchKernelGGL(gftt_eig_masked_kernel<false>, grid, block, 0, s, a);
     } else {
@@ -1268,9 +1322,9 @@ hipError_t launch_gftt_eig(const GfttArgs& a, hipStream_t s)
     return hipGetLastError();
 }
 
-hipError_t launch_gftt(const GfttArgs& a, hipStream_t s, hipEvent_t after_eig)
+hipError_t launch_gftt(const GfttArgs& a, hipStream_t s, hipEvent_t after_eig, int pix)
 {
-    const hipError_t e0 = launch_gftt_eig(a, s);
+    const hipError_t e0 = launch_gftt_eig(a, s, pix);
     if (e0 != hipSuccess) return e0;
     if (after_eig) {
         const hipError_t e = hipEventRecord(after_eig, s);

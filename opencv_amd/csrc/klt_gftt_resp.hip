@@ -19,6 +19,8 @@
 //   4. gftt_resp_lmax   : per 56-column strip, the maximum key and the 3x3
 //                         local-maximum ballots in gftt_eig_kernel's layout, so
 //                         gftt_select_kernel runs unchanged on the result.
+// A 16U or 32F image (tbdk_gftt_rois_px, tbdk_corner_response_px) differs in step 1
+// only: gftt_resp_covpx_kernel<T> (scale without the 1/255, the float row filter).
 // These ROIs are rare (the TBD loop and the sample use blockSize 3, min
 // eigenvalue); the launches are correct-first: HBM traffic 36 B/px of scratch
 // (cov 12 + row sums 24) on top of the eigenvalue plane.
@@ -90,6 +92,39 @@ __global__ __launch_bounds__(256) void gftt_resp_cov_kernel(GfttRespArgs a)
         u = u + k2 * s1;
         u = u + k * s2;
         ry[j] = u;
+    }
+    const float dx = (rx[0] + rx[2]) * k + (rx[1] * k2 + 0.f);
+    const float dy = (ry[2] - ry[0]) + 0.f;
+    float* c = a.cov + 3 * ((size_t)R.off + i);
+    c[0] = dx * dx;
+    c[1] = dx * dy;
+    c[2] = dy * dy;
+}
+
+// ... of a 16U (T = uint16_t) or 32F (float) image (tbdk_corner_response_px,
+// tbdk_gftt_rois_px): a.pitch in bytes, a.k / a.k2 without the 8-bit path's
+// 1/255, and the reference's float ksize-3 row filter (SymmRowSmallFilter,
+// filter.simd.hpp:1708-1743, 2425-2469, unfused): rx = S[x+1] - S[x-1],
+// ry = S[x]*k0 + (S[x-1] + S[x+1])*k1
+template <typename T>
+__global__ __launch_bounds__(256) void gftt_resp_covpx_kernel(GfttRespArgs a)
+{
+    const GfttRoi R = a.rois[blockIdx.y];
+    const int i = blockIdx.x * 256 + threadIdx.x;
+    if (i >= R.w * R.h) return;
+    const int y = i / R.w, x = i - y * R.w;
+    const uint8_t* base = a.img + (size_t)R.y * a.pitch + (size_t)R.x * sizeof(T);
+    const T* rr[3] = {reinterpret_cast<const T*>(base + (size_t)rrefl(y - 1, R.h) * a.pitch),
+                      reinterpret_cast<const T*>(base + (size_t)y * a.pitch),
+                      reinterpret_cast<const T*>(base + (size_t)rrefl(y + 1, R.h) * a.pitch)};
+    const int xl = rrefl(x - 1, R.w), xr = rrefl(x + 1, R.w);
+    const float k = a.k, k2 = a.k2;
+    float rx[3], ry[3];
+#pragma unroll
+    for (int j = 0; j < 3; ++j) {
+        const float s0 = (float)rr[j][xl], s1 = (float)rr[j][x], s2 = (float)rr[j][xr];
+        rx[j] = s2 - s0;
+        ry[j] = s1 * k2 + (s0 + s2) * k;
     }
     const float dx = (rx[0] + rx[2]) * k + (rx[1] * k2 + 0.f);
     const float dy = (ry[2] - ry[0]) + 0.f;
@@ -239,11 +274,13 @@ __global__ __launch_bounds__(64) void gftt_resp_lmax_kernel(GfttRespArgs a)
     if (lane == 0) a.blk_max[blockIdx.x] = best;
 }
 
-hipError_t launch_gftt_resp(const GfttRespArgs& a, int ncblk, int max_w, int max_h, int max_area, hipStream_t s)
+hipError_t launch_gftt_resp(const GfttRespArgs& a, int ncblk, int max_w, int max_h, int max_area, hipStream_t s, int pix)
 {
     if (a.nroi <= 0) return hipSuccess;
     const dim3 gpx((max_area + 255) / 256, a.nroi);
-    hipLaunchKernelGGL(gftt_resp_cov_kernel, gpx, dim3(256), 0, s, a);
+    if (pix == TBDK_PIX_F32) hipLaunchKernelGGL(gftt_resp_covpx_kernel<float>, gpx, dim3(256), 0, s, a);
+    else if (pix == TBDK_PIX_U16) hipLaunchKernelGGL(gftt_resp_covpx_kernel<uint16_t>, gpx, dim3(256), 0, s, a);
+    else hipLaunchKernelGGL(gftt_resp_cov_kernel, gpx, dim3(256), 0, s, a);
     if (a.block == 3 || a.block == 5)
         hipLaunchKernelGGL(gftt_resp_rowsum_px_kernel, gpx, dim3(256), 0, s, a);
     else

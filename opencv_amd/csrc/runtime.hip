@@ -821,7 +821,7 @@ int gftt_prepare(const tbdk_roi* rois, int nroi, int width, int height, const tb
 
 static void gftt_resp_args(GfttRespArgs& ra, const GfttScratch& sc, const uint8_t* img, int pitch,
                            const GfttRoi* d_rois, int nroi, int block, int harris, double hk,
-                           const uint8_t* mask = nullptr, int mask_pitch = 0)
+                           const uint8_t* mask = nullptr, int mask_pitch = 0, int pix = TBDK_PIX_U8)
 {
     ra.mask = mask;
     ra.mask_pitch = mask_pitch;
@@ -836,8 +836,8 @@ static void gftt_resp_args(GfttRespArgs& ra, const GfttScratch& sc, const uint8_
     ra.lmax = static_cast<uint64_t*>(sc.cand);
     ra.block = block;
     ra.harris = harris;
-    // cornerEigenValsVecs' scale for ksize 3 on 8-bit input (corner.cpp:248-255)
-    const double scale = 1.0 / ((double)(1 << 2) * block * 255.0);
+    // cornerEigenValsVecs' scale for ksize 3 (corner.cpp:248-255): the x 255 on 8-bit input only
+    const double scale = pix == TBDK_PIX_U8 ? 1.0 / ((double)(1 << 2) * block * 255.0) : 1.0 / ((double)(1 << 2) * block);
     ra.k = (float)(1.0 * scale);
     ra.k2 = (float)(2.0 * scale);
     ra.kf = (float)hk;
@@ -892,7 +892,8 @@ int gftt_reserve(GfttScratch& sc, int device, int max_rois, int64_t max_px)
 
 int gftt_launch(tbdk_ctx* ctx, GfttScratch& sc, const uint8_t* img, int pitch, const GfttRoi* d_rois,
                 const GfttPlan& plan, const tbdk_gftt_params* p, float* corners, int32_t* counts, hipStream_t s,
-                hipEvent_t after_eig, int corner_stride, const GfttRoi* h_rois, const uint8_t* mask, int mask_pitch)
+                hipEvent_t after_eig, int corner_stride, const GfttRoi* h_rois, const uint8_t* mask, int mask_pitch,
+                int pix)
 {
     if (corner_stride != 0 && corner_stride < p->max_corners) return TBDK_EINVAL;
     int rc = gftt_reserve(sc, ctx->device, plan.nroi, plan.total);
@@ -933,14 +934,14 @@ int gftt_launch(tbdk_ctx* ctx, GfttScratch& sc, const uint8_t* img, int pitch, c
     gftt_plan(a, plan.max_area);
     hipError_t e;
     if (!gftt_generic(p)) {
-        e = launch_gftt(a, s, after_eig);
+        e = launch_gftt(a, s, after_eig, pix);
     } else {
         rc = gftt_reserve_resp(sc, ctx->device, plan.total);
         if (rc != TBDK_OK) return rc;
         GfttRespArgs ra;
         gftt_resp_args(ra, sc, img, pitch, d_rois, plan.nroi, p->block_size, p->use_harris, p->harris_k, a.mask,
-                       a.mask_pitch);
-        e = launch_gftt_resp(ra, plan.ncblk, plan.max_w, plan.max_h, plan.max_area, s);
+                       a.mask_pitch, pix);
+        e = launch_gftt_resp(ra, plan.ncblk, plan.max_w, plan.max_h, plan.max_area, s, pix);
         if (e == hipSuccess && after_eig) e = hipEventRecord(after_eig, s);
         if (e == hipSuccess) e = launch_gftt_select(a, s);
     }
@@ -968,10 +969,30 @@ int tbdk_gftt_rois_masked(tbdk_ctx* ctx, const uint8_t* img, int width, int heig
                           int mask_pitch, const tbdk_roi* rois, int nroi, const tbdk_gftt_params* p, float* corners,
                           int32_t* counts, void* stream)
 {
-    if (!ctx || !p || nroi < 0) return TBDK_EINVAL;
+    return tbdk_gftt_rois_px(ctx, img, TBDK_PIX_U8, width, height, pitch, mask, mask_pitch, rois, nroi, p, corners,
+                             counts, stream);
+}
+
+// bytes per pixel of a TBDK_PIX_* image, 0 for an unknown type
+static int pix_bytes(int pix) { return pix == TBDK_PIX_U8 ? 1 : pix == TBDK_PIX_U16 ? 2 : pix == TBDK_PIX_F32 ? 4 : 0; }
+// an image pointer and pitch of that type: aligned to the pixel, a row fits the pitch
+static bool pix_layout_ok(const void* img, int pix, int width, int pitch)
+{
+    const int b = pix_bytes(pix);
+    return b != 0 && reinterpret_cast<uintptr_t>(img) % (uintptr_t)b == 0 && pitch % b == 0 &&
+           (int64_t)pitch >= (int64_t)width * b;
+}
+
+int tbdk_gftt_rois_px(tbdk_ctx* ctx, const void* img_, int pix, int width, int height, int pitch, const uint8_t* mask,
+                      int mask_pitch, const tbdk_roi* rois, int nroi, const tbdk_gftt_params* p, float* corners,
+                      int32_t* counts, void* stream)
+{
+    const uint8_t* img = static_cast<const uint8_t*>(img_);
+    if (!ctx || !p || nroi < 0 || pix_bytes(pix) == 0) return TBDK_EINVAL;
     if (mask && mask_pitch < width) return TBDK_EINVAL;
     if (nroi == 0) return TBDK_OK;
-    if (!img || !rois || !corners || !counts || width <= 0 || height <= 0 || pitch < width) return TBDK_EINVAL;
+    if (!img || !rois || !corners || !counts || width <= 0 || height <= 0 || !pix_layout_ok(img, pix, width, pitch))
+        return TBDK_EINVAL;
     GfttPlan plan;
     std::vector<GfttRoi> tab((size_t)nroi);
     int rc = gftt_prepare(rois, nroi, width, height, p, tab.data(), &plan);
@@ -984,14 +1005,14 @@ int tbdk_gftt_rois_masked(tbdk_ctx* ctx, const uint8_t* img, int width, int heig
     hipError_t e = hipMemcpyAsync(ctx->gftt.rois, tab.data(), sizeof(GfttRoi) * (size_t)nroi, hipMemcpyHostToDevice, s);
     if (e != hipSuccess) return map_err(e);
     return gftt_launch(ctx, ctx->gftt, img, pitch, static_cast<const GfttRoi*>(ctx->gftt.rois), plan, p, corners,
-                       counts, s, nullptr, 0, tab.data(), mask, mask_pitch);
+                       counts, s, nullptr, 0, tab.data(), mask, mask_pitch, pix);
 }
 
-int tbdk_corner_min_eig_val(tbdk_ctx* ctx, const uint8_t* img, int width, int height, int pitch, float* dst,
-                            int dst_pitch, void* stream)
+static int corner_min_eig_px(tbdk_ctx* ctx, const uint8_t* img, int pix, int width, int height, int pitch, float* dst,
+                             int dst_pitch, void* stream)
 {
-    if (!ctx || !img || !dst || width <= 0 || height <= 0 || pitch < width || dst_pitch < width * 4 ||
-        dst_pitch % 4 != 0)
+    if (!ctx || !img || !dst || width <= 0 || height <= 0 || !pix_layout_ok(img, pix, width, pitch) ||
+        dst_pitch < width * 4 || dst_pitch % 4 != 0)
         return TBDK_EINVAL;
     tbdk_roi roi{0, 0, width, height};
     tbdk_gftt_params p{1, 0.01, 0.0, 3};
@@ -1016,7 +1037,7 @@ int tbdk_corner_min_eig_val(tbdk_ctx* ctx, const uint8_t* img, int width, int he
     a.blk_max = ctx->gftt.blk;
     a.lmax = static_cast<uint64_t*>(ctx->gftt.cand);
     a.eig_redo = ctx->opt_gftt_eig_redo;
-    e = launch_gftt_eig(a, s);
+    e = launch_gftt_eig(a, s, pix);
     timing_end(ctx, rec, s);
     if (e == hipSuccess)
         e = hipMemcpy2DAsync(dst, (size_t)dst_pitch, ctx->gftt.planes, (size_t)gftt_epitch(width) * 4, (size_t)width * 4, height,
@@ -1024,14 +1045,28 @@ int tbdk_corner_min_eig_val(tbdk_ctx* ctx, const uint8_t* img, int width, int he
     return map_err(e);
 }
 
+int tbdk_corner_min_eig_val(tbdk_ctx* ctx, const uint8_t* img, int width, int height, int pitch, float* dst,
+                            int dst_pitch, void* stream)
+{
+    return corner_min_eig_px(ctx, img, TBDK_PIX_U8, width, height, pitch, dst, dst_pitch, stream);
+}
+
 int tbdk_corner_response(tbdk_ctx* ctx, const uint8_t* img, int width, int height, int pitch, float* dst,
                          int dst_pitch, int block_size, int harris, double harris_k, void* stream)
 {
-    if (!ctx || !img || !dst || width <= 0 || height <= 0 || pitch < width || dst_pitch < width * 4 ||
-        dst_pitch % 4 != 0 || block_size < 1 || block_size > 63 || !std::isfinite(harris_k))
+    return tbdk_corner_response_px(ctx, img, TBDK_PIX_U8, width, height, pitch, dst, dst_pitch, block_size, harris,
+                                   harris_k, stream);
+}
+
+int tbdk_corner_response_px(tbdk_ctx* ctx, const void* img_, int pix, int width, int height, int pitch, float* dst,
+                            int dst_pitch, int block_size, int harris, double harris_k, void* stream)
+{
+    const uint8_t* img = static_cast<const uint8_t*>(img_);
+    if (!ctx || !img || !dst || width <= 0 || height <= 0 || !pix_layout_ok(img, pix, width, pitch) ||
+        dst_pitch < width * 4 || dst_pitch % 4 != 0 || block_size < 1 || block_size > 63 || !std::isfinite(harris_k))
         return TBDK_EINVAL;
     if (block_size == 3 && !harris)
-        return tbdk_corner_min_eig_val(ctx, img, width, height, pitch, dst, dst_pitch, stream);
+        return corner_min_eig_px(ctx, img, pix, width, height, pitch, dst, dst_pitch, stream);
     tbdk_roi roi{0, 0, width, height};
     tbdk_gftt_params p{1, 0.01, 0.0, block_size, harris ? 1 : 0, harris_k};
     GfttPlan plan;
@@ -1048,8 +1083,8 @@ int tbdk_corner_response(tbdk_ctx* ctx, const uint8_t* img, int width, int heigh
     int rec = timing_begin(ctx, "corner_response", s);
     GfttRespArgs ra;
     gftt_resp_args(ra, ctx->gftt, img, pitch, static_cast<const GfttRoi*>(ctx->gftt.rois), 1, block_size,
-                   harris ? 1 : 0, harris_k);
-    e = launch_gftt_resp(ra, plan.ncblk, plan.max_w, plan.max_h, plan.max_area, s);
+                   harris ? 1 : 0, harris_k, nullptr, 0, pix);
+    e = launch_gftt_resp(ra, plan.ncblk, plan.max_w, plan.max_h, plan.max_area, s, pix);
     timing_end(ctx, rec, s);
     if (e == hipSuccess)
         e = hipMemcpy2DAsync(dst, (size_t)dst_pitch, ctx->gftt.planes, (size_t)gftt_epitch(width) * 4, (size_t)width * 4, height,

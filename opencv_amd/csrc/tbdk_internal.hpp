@@ -415,9 +415,12 @@ void gftt_scratch_free(GfttScratch& sc);
 int gftt_launch(tbdk_ctx* ctx, GfttScratch& sc, const uint8_t* img, int pitch, const GfttRoi* d_rois, const GfttPlan& plan,
                 const tbdk_gftt_params* p, float* corners, int32_t* counts, hipStream_t s,
                 hipEvent_t after_eig = nullptr, int corner_stride = 0,  // 0: max_corners
-                const GfttRoi* h_rois = nullptr, const uint8_t* mask = nullptr, int mask_pitch = 0);
-hipError_t launch_gftt(const GfttArgs& a, hipStream_t s, hipEvent_t after_eig = nullptr);
-hipError_t launch_gftt_eig(const GfttArgs& a, hipStream_t s);  // eigenvalue planes only
+                const GfttRoi* h_rois = nullptr, const uint8_t* mask = nullptr, int mask_pitch = 0,
+                int pix = TBDK_PIX_U8);
+// pix (TBDK_PIX_*): the pixel type of a.img, a.pitch in bytes; the 16U / 32F
+// launches are kernel instances of their own, the arguments are the same
+hipError_t launch_gftt(const GfttArgs& a, hipStream_t s, hipEvent_t after_eig = nullptr, int pix = TBDK_PIX_U8);
+hipError_t launch_gftt_eig(const GfttArgs& a, hipStream_t s, int pix = TBDK_PIX_U8);  // eigenvalue planes only
 hipError_t launch_gftt_select(const GfttArgs& a, hipStream_t s);
 // blockSize != 3 or Harris (klt_gftt_resp.hip): the response plane, strip
 // maxima and local-maximum words in gftt_eig_kernel's layout
@@ -439,7 +442,8 @@ struct GfttRespArgs {
     const uint8_t* mask;  // optional corner mask (GfttArgs::mask), read by the strip maxima only
     int mask_pitch;
 };
-hipError_t launch_gftt_resp(const GfttRespArgs& a, int ncblk, int max_w, int max_h, int max_area, hipStream_t s);
+hipError_t launch_gftt_resp(const GfttRespArgs& a, int ncblk, int max_w, int max_h, int max_area, hipStream_t s,
+                            int pix = TBDK_PIX_U8);
 int gftt_reserve_resp(GfttScratch& sc, int device, int64_t max_px);
 inline bool gftt_generic(const tbdk_gftt_params* p) { return p->block_size != 3 || p->use_harris != 0; }
 }  // namespace tbdk

@@ -246,11 +246,27 @@ def pyr_down(src: torch.Tensor, ctx: Context | None = None, stream=None) -> torc
     return dst
 
 
+_PIX = {torch.uint8: _lib.TBDK_PIX_U8, torch.uint16: _lib.TBDK_PIX_U16, torch.float32: _lib.TBDK_PIX_F32}
+
+
+def _corner_image(img: torch.Tensor, what: str) -> tuple[int, int]:
+    """(pix, row pitch in bytes) of a GFTT / corner-map source: a 2-D uint8,
+    uint16 or float32 device tensor with stride(1) == 1 (any row stride; the
+    library checks pointer and pitch against the pixel's alignment)"""
+    if not isinstance(img, torch.Tensor) or img.dtype not in _PIX or img.dim() != 2 or not img.is_cuda or \
+            img.stride(1) != 1:
+        raise _lib.TbdkError(f"{what} expects a 2-D uint8, uint16 or float32 device tensor")
+    return _PIX[img.dtype], img.stride(0) * img.element_size()
+
+
 def corner_min_eigen_val(src: torch.Tensor, ctx: Context | None = None, stream=None) -> torch.Tensor:
-    """cv::cuda::createMinEigenValCorner(CV_8UC1, 3, 3)->compute: float32 (h, w)
-    minimum-eigenvalue map, bit-exact with the CPU cornerMinEigenVal."""
+    """cv::cuda::createMinEigenValCorner(CV_8UC1 / CV_32FC1, 3, 3)->compute: float32 (h, w)
+    minimum-eigenvalue map, bit-exact with the CPU cornerMinEigenVal.  A uint16
+    source gives the float32 result of the same values."""
+    if isinstance(src, torch.Tensor) and src.dtype != torch.uint8:
+        return corner_response(src, 3, False, ctx=ctx, stream=stream)
     if src.dtype != torch.uint8 or src.dim() != 2 or not src.is_cuda or src.stride(1) != 1:
-        raise _lib.TbdkError("corner_min_eigen_val expects a 2-D uint8 device tensor")
+        raise _lib.TbdkError("corner_min_eigen_val expects a 2-D uint8, uint16 or float32 device tensor")
     ctx = ctx or Context.get(src.device.index or 0)
     h, w = src.shape
     dst = torch.empty((h, w), dtype=torch.float32, device=src.device)
@@ -262,18 +278,25 @@ def corner_min_eigen_val(src: torch.Tensor, ctx: Context | None = None, stream=N
 
 def corner_response(src: torch.Tensor, block_size: int = 3, harris: bool = False, k: float = 0.04,
                     ctx: Context | None = None, stream=None) -> torch.Tensor:
-    """cv::cuda::createMinEigenValCorner(CV_8UC1, blockSize, 3) / createHarrisCorner(CV_8UC1,
-    blockSize, 3, k) ->compute (cudaimgproc.hpp:548-566): float32 (h, w) response map with
-    the CPU cornerMinEigenVal / cornerHarris numerics (corner.cpp:52-152,237-326)."""
-    if src.dtype != torch.uint8 or src.dim() != 2 or not src.is_cuda or src.stride(1) != 1:
-        raise _lib.TbdkError("corner_response expects a 2-D uint8 device tensor")
+    """cv::cuda::createMinEigenValCorner(srcType, blockSize, 3) / createHarrisCorner(srcType,
+    blockSize, 3, k) ->compute (cudaimgproc.hpp:548-566), srcType CV_8UC1 or CV_32FC1: float32
+    (h, w) response map with the CPU cornerMinEigenVal / cornerHarris numerics
+    (corner.cpp:52-152,237-326).  A uint16 source gives the float32 result of the same
+    values; float pixels must be finite."""
+    pix, pitch = _corner_image(src, "corner_response")
     ctx = ctx or Context.get(src.device.index or 0)
     h, w = src.shape
     dst = torch.empty((h, w), dtype=torch.float32, device=src.device)
-    _lib.check(ctx.lib.tbdk_corner_response(ctx.handle, C.c_void_p(src.data_ptr()), w, h, src.stride(0),
-                                            C.c_void_p(dst.data_ptr()), dst.stride(0) * 4, int(block_size),
-                                            1 if harris else 0, float(k), _stream_ptr(stream)),
-               "tbdk_corner_response")
+    if pix == _lib.TBDK_PIX_U8:
+        _lib.check(ctx.lib.tbdk_corner_response(ctx.handle, C.c_void_p(src.data_ptr()), w, h, pitch,
+                                                C.c_void_p(dst.data_ptr()), dst.stride(0) * 4, int(block_size),
+                                                1 if harris else 0, float(k), _stream_ptr(stream)),
+                   "tbdk_corner_response")
+    else:
+        _lib.check(ctx.lib.tbdk_corner_response_px(ctx.handle, C.c_void_p(src.data_ptr()), pix, w, h, pitch,
+                                                   C.c_void_p(dst.data_ptr()), dst.stride(0) * 4, int(block_size),
+                                                   1 if harris else 0, float(k), _stream_ptr(stream)),
+                   "tbdk_corner_response_px")
     return dst
 
 
@@ -634,12 +657,14 @@ class DensePyrLKOpticalFlow(SparsePyrLKOpticalFlow):
 
 
 class GoodFeaturesToTrackDetector:
-    """cv::cuda::createGoodFeaturesToTrackDetector(CV_8UC1, maxCorners, qualityLevel,
+    """cv::cuda::createGoodFeaturesToTrackDetector(srcType, maxCorners, qualityLevel,
     minDistance, blockSize=3, useHarrisDetector=False, harrisK=0.04)
     (cudaimgproc.hpp:603-604) with the CPU goodFeaturesToTrack semantics, applied
     to a batch of box ROIs of one image, optionally under an 8-bit mask
     (goodFeaturesToTrack's `mask`: the quality threshold comes from the maximum
-    over the masked-in pixels, and only they can be corners)."""
+    over the masked-in pixels, and only they can be corners).  The image is
+    uint8 (CV_8UC1), float32 (CV_32FC1, finite pixels) or uint16 (the float32
+    result of the same values)."""
 
     def __init__(self, maxCorners: int = 1000, qualityLevel: float = 0.01, minDistance: float = 0.0,
                  blockSize: int = 3, useHarrisDetector: bool = False, harrisK: float = 0.04, device: int = 0):
@@ -652,9 +677,10 @@ class GoodFeaturesToTrackDetector:
         counts (nroi,) i32) device tensors; corners are in image coordinates.
         mask: optional 2-D uint8 device tensor of the image's shape with
         stride(1) == 1 (any row stride: a slice of a larger tensor works); each
-        ROI reads its own rectangle of it (tbdk_gftt_rois_masked)."""
-        if image.dtype != torch.uint8 or image.dim() != 2 or not image.is_cuda or image.stride(1) != 1:
-            raise _lib.TbdkError("detect expects a 2-D uint8 device tensor")
+        ROI reads its own rectangle of it (tbdk_gftt_rois_masked).
+        image: 2-D uint8, uint16 or float32 device tensor with stride(1) == 1
+        (the wider types through tbdk_gftt_rois_px)."""
+        pix, pitch = _corner_image(image, "detect")
         if mask is not None and (not isinstance(mask, torch.Tensor) or mask.dtype != torch.uint8 or mask.dim() != 2 or
                                  mask.device != image.device or mask.shape != image.shape or mask.stride(1) != 1):
             raise _lib.TbdkError("mask must be a 2-D uint8 tensor of the image's shape on its device, stride(1) == 1")
@@ -663,7 +689,14 @@ class GoodFeaturesToTrackDetector:
         arr = (_lib.Roi * max(n, 1))(*[_lib.Roi(int(x), int(y), int(w), int(h)) for (x, y, w, h) in rois])
         corners = torch.zeros((n, self.prm.max_corners, 2), dtype=torch.float32, device=image.device)
         counts = torch.zeros((n,), dtype=torch.int32, device=image.device)
-        if mask is None:
+        if pix != _lib.TBDK_PIX_U8:
+            _lib.check(self.ctx.lib.tbdk_gftt_rois_px(
+                self.ctx.handle, C.c_void_p(image.data_ptr()), pix, image.shape[1], image.shape[0], pitch,
+                C.c_void_p(mask.data_ptr()) if mask is not None else None,
+                int(mask.stride(0)) if mask is not None else 0, arr, n, C.byref(self.prm),
+                C.c_void_p(corners.data_ptr()), C.c_void_p(counts.data_ptr()), _stream_ptr(stream)),
+                "tbdk_gftt_rois_px")
+        elif mask is None:
             _lib.check(self.ctx.lib.tbdk_gftt_rois(self.ctx.handle, C.c_void_p(image.data_ptr()), image.shape[1],
                                                    image.shape[0], image.stride(0), arr, n, C.byref(self.prm),
                                                    C.c_void_p(corners.data_ptr()), C.c_void_p(counts.data_ptr()),

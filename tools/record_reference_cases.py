@@ -2,7 +2,8 @@
 """Records the real reference (buildOpticalFlowPyramid, calcOpticalFlowPyrLK,
 goodFeaturesToTrack, cornerMinEigenVal / cornerHarris, warpAffine,
 calcOpticalFlowFarneback, HOGDescriptor) on the cases of tests/_reference_cases.py
-(goodFeaturesToTrack under a mask: tests/_gftt_mask_cases.py)
+(goodFeaturesToTrack under a mask: tests/_gftt_mask_cases.py; the corner maps and
+goodFeaturesToTrack on CV_32F images: tests/_gftt_f32_cases.py)
 into tests/golden/reference_<op>.npz, through tools/reference_driver.cpp (how to
 build it: tools/record_reference_cases.md).
 
@@ -36,12 +37,13 @@ sys.path.insert(0, os.path.join(ROOT, "tests"))
 import _oracle as O  # noqa: E402
 import _reference_cases as RC  # noqa: E402
 import _gftt_mask_cases as MC  # noqa: E402
+import _gftt_f32_cases as FC  # noqa: E402
 
 LIMIT = 256 * 1024
 STATES = ("default", "noavx2")
 # the state each oracle file models where the two differ (README, numerics)
 MODELLED = {"pyramid": "both", "pyrlk": "both", "warpaffine": "both", "gftt": "noavx2", "gftt_mask": "noavx2",
-            "cornermaps": "noavx2",
+            "cornermaps": "noavx2", "gftt_f32": "noavx2",
             "farneback": "noavx2", "farneback_box": "noavx2", "hog": "default"}
 
 
@@ -191,6 +193,28 @@ def rec_cornermaps(d):
     return cases, dict(meta=np.array(meta, np.int32))
 
 
+def rec_gftt_f32(d):
+    """cornerMinEigenVal / cornerHarris and goodFeaturesToTrack on CV_32F images
+    (tests/_gftt_f32_cases.py): the maps first, then the lists"""
+    cases = []
+    for h, w, kind, block, harris in FC.map_cases():
+        img = np.ascontiguousarray(FC.map_image(h, w, kind), dtype=np.float32)
+        _, rd = d.run("cmap", dict(a=img), w=w, h=h, depth="32f", block=block, harris=harris, k=FC.HARRIS_K)
+        cases.append(({}, dict(e=rd("e", np.float32).reshape(h, w))))
+    for kind, r, mk, maxc, ql, md, block, harris in FC.list_cases():
+        roi = np.ascontiguousarray(FC.list_image(kind, r), dtype=np.float32)
+        h, w = roi.shape
+        files = dict(a=roi)
+        if mk != "none":
+            files["mask"] = FC.list_mask(mk, w, h)
+        _, rd = d.run("gftt", files, w=w, h=h, depth="32f", maxc=maxc, ql=ql, md=md, block=block, harris=harris,
+                      k=FC.HARRIS_K)
+        c = rd("c", np.float32).reshape(-1, 2)
+        assert np.array_equal(c, c.astype(np.uint16))
+        cases.append((dict(c=c.astype(np.uint16)), {}))
+    return cases, dict(nmaps=np.array(len(FC.map_cases()), np.int32))
+
+
 def warp_table():
     """(flags, border, bval, sw, sh, dw, dh, M) per case: 4 interpolations x 6 borders x
     the inverse flag on matrices drawn from a fixed seed, then the degenerate matrices"""
@@ -322,13 +346,14 @@ def merge(op, rec, whole_limit):
 
 
 RECORDERS = {"pyramid": rec_pyramid, "pyrlk": rec_pyrlk, "gftt": rec_gftt, "gftt_mask": rec_gftt_mask,
-             "cornermaps": rec_cornermaps,
+             "cornermaps": rec_cornermaps, "gftt_f32": rec_gftt_f32,
              "warpaffine": rec_warpaffine, "farneback": rec_farneback, "farneback_box": rec_farneback_box,
              "hog": rec_hog}
 # bytes up to which an output is stored whole (tests/_reference_cases.py: WHOLE_LIMIT).  The kernels are
 # compared with the box Farneback flows within a tolerance, so all six stay whole (about 7 KB under LIMIT)
 WHOLE = {"farneback": 20480, "farneback_box": 72800, "pyrlk": 1 << 20, "gftt": 1 << 20, "gftt_mask": 1 << 20,
          "hog": 16384}
+# (gftt_f32: maps above RC.WHOLE_LIMIT as row CRCs; its corner lists are far below it)
 
 
 def save(path, arrays):
@@ -351,6 +376,13 @@ def case_label(op, i):
     if op == "gftt_mask":
         r, m, maxc, ql, md, block, harris = MC.cases()[i]
         return f"roi {r} mask {MC.masks()[m][1]} ({maxc}, {ql}, {md}) block {block}" + (" harris" if harris else "")
+    if op == "gftt_f32":
+        nm = len(FC.map_cases())
+        if i < nm:
+            h, w, kind, block, harris = FC.map_cases()[i]
+            return f"{kind} {h}x{w} block {block} " + ("harris" if harris else "minEigenVal")
+        kind, r, mk, maxc, ql, md, block, harris = FC.list_cases()[i - nm]
+        return f"{kind} roi {r} mask {mk} ({maxc}, {ql}, {md}) block {block}" + (" harris" if harris else "")
     if op == "cornermaps":
         w, h, _ = RC.CMAP_SHAPES[i // len(RC.CMAP_MODES)]
         block, harris = RC.CMAP_MODES[i % len(RC.CMAP_MODES)]

@@ -5,16 +5,17 @@
 //
 //   reference_driver <op> <out-prefix> key=value ...
 //
-// Images are raw 8-bit files (rows of w * cn bytes); every output goes to
+// Images are raw 8-bit files (rows of w * cn bytes), or, for gftt and cmap with
+// depth=32f, raw float32 files of one channel; every output goes to
 // <out-prefix>.<name> as raw little-endian data.  The first line printed is the
 // runtime dispatch state, "SSE4_1=. AVX=. AVX2=. FMA3=."; the caller checks it.
 //
 //   pyr   a= w= h= cn= winw= winh= maxl=           -> L<i> (u8), D<i> (i16, 2cn per pixel); prints the level sizes
 //   lk    a= b= w= h= cn= winw= winh= maxl= flags= pts= n= [init=] err=0|1
 //                                                  -> q (f32 pairs), st (u8), err (f32, if err=1)
-//   gftt  a= w= h= maxc= ql= md= block= harris= k= [mask=] -> c (f32 pairs); prints the count
+//   gftt  a= w= h= maxc= ql= md= block= harris= k= [mask=] [depth=8u|32f] -> c (f32 pairs); prints the count
 //                                                  (mask: raw u8, w x h, goodFeaturesToTrack's mask)
-//   cmap  a= w= h= block= harris= k=               -> e (f32): cornerMinEigenVal / cornerHarris, ksize 3
+//   cmap  a= w= h= block= harris= k= [depth=8u|32f] -> e (f32): cornerMinEigenVal / cornerHarris, ksize 3
 //   warp  a= w= h= m= (6 doubles, raw) dst= dw= dh= flags= border= bval=   -> w (u8)
 //   fb    a= b= w= h= ps= lv= ws= it= pn= sg= flags= [init=]               -> f (f32 pairs)
 //   hoggrad a= w= h= cn= gamma= signed=            -> g (f32 pairs), qa (u8 pairs)
@@ -72,10 +73,20 @@ static Mat image(const std::string& key, int w, int h, int cn)
     return m;
 }
 
+// the source image of gftt / cmap: CV_8UC1, or CV_32FC1 with depth=32f
+static Mat image_depth(const std::string& key, int w, int h)
+{
+    if (!has("depth") || arg("depth") == "8u") return image(key, w, h, 1);
+    if (arg("depth") != "32f") throw std::runtime_error("depth must be 8u or 32f");
+    Mat m(h, w, CV_32FC1);
+    rd(arg(key), m.data, (size_t)w * h * 4);
+    return m;
+}
+
 static int run(const std::string& op, const std::string& out)
 {
     const int w = iarg("w"), h = iarg("h"), cn = has("cn") ? iarg("cn") : 1;
-    Mat a = image("a", w, h, cn);
+    Mat a = op == "gftt" || op == "cmap" ? image_depth("a", w, h) : image("a", w, h, cn);
     if (op == "pyr") {
         std::vector<Mat> pyr;
         int top = buildOpticalFlowPyramid(a, pyr, Size(iarg("winw"), iarg("winh")), iarg("maxl"), true);
