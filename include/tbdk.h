@@ -241,6 +241,14 @@ int tbdk_ctx_set_option(tbdk_ctx* ctx, const char* name, int64_t value);
  *       the kept pairs only.  tbdk_frame_metrics: lk_points counts the points
  *       entering the forward pass, klt_points the pairs kept after the check,
  *       lk_iters the forward pass's iterations.
+ *   "tbd_subpix" (0..15, default 0; taken by tbdk_tbd_create): 0: off; N > 0:
+ *       every corner set the TBD loop's GFTT produces is refined by
+ *       tbdk_corner_sub_pix on the frame it was detected on (the whole frame,
+ *       not the ROI as an isolated image), window (N, N), no zero zone,
+ *       criteria (COUNT|EPS, 20, 0.03), before PyrLK reads it; N = 10 is the
+ *       call of the reference's KLT sample (samples/cpp/lkdemo.cpp:85).  The
+ *       corner mask does not apply to the refinement.  Frames smaller than
+ *       2N + 5 in either dimension make tbdk_tbd_create return TBDK_EINVAL.
  *   "timing_every" (>= 1, default 1): HIP events on a pseudo-random 1/N of the
  *       launches of each kernel selected for timing: launch i (counted per
  *       kernel name from tbdk_timing_enable) is timed iff splitmix64(i) % N == 0
@@ -554,6 +562,50 @@ int tbdk_gftt_rois_px(tbdk_ctx* ctx, const void* img, int pix, int width, int he
                       float* corners, int32_t* counts, void* stream);
 int tbdk_corner_response_px(tbdk_ctx* ctx, const void* img, int pix, int width, int height, int pitch,
                             float* dst, int dst_pitch, int block_size, int harris, double harris_k, void* stream);
+
+/* ---- sub-pixel corner refinement ----------------------------------------------- */
+
+/* cv::cornerSubPix(image, corners, winSize, zeroZone, criteria)
+ * (imgproc/include/opencv2/imgproc.hpp; imgproc/src/cornersubpix.cpp:44-156) */
+typedef struct tbdk_subpix_params {
+    int32_t win_w, win_h;        /* half sizes, 1..15 each (the window is 2*win+1) */
+    int32_t zero_w, zero_h;      /* half sizes of the zero zone; (-1,-1): none */
+    int32_t criteria;            /* 1 COUNT, 2 EPS, 3 both (cv::TermCriteria::Type) */
+    int32_t max_count;
+    double  epsilon;
+} tbdk_subpix_params;
+/* the call of the reference's KLT sample (samples/cpp/lkdemo.cpp:85):
+ * (10,10), (-1,-1), COUNT|EPS, 20, 0.03 */
+int tbdk_subpix_default_params(tbdk_subpix_params* p);
+/* Replaces cv::cornerSubPix on a batch of point rows, on the device and with no
+ * host synchronisation; the reference has a CPU implementation only, and every
+ * refined point equals its result bit for bit (TBDK_PIX_U8 and TBDK_PIX_F32;
+ * TBDK_PIX_U16, which the reference rejects, gives the F32 result of the same
+ * pixel values).
+ *   img      : device one-channel image (pix: TBDK_PIX_*; pitch in bytes)
+ *   corners  : device, nrows x row_cap x float2, refined in place
+ *   counts   : device, nrows int32, as tbdk_gftt_rois writes them: the first
+ *              counts[r] points of row r are refined; counts[r] <= 0 (the -1
+ *              overflow mark included) leaves the row untouched, larger values
+ *              are clamped to row_cap.  NULL: every row is full (a flat list
+ *              of n points is nrows = 1, row_cap = n).
+ * A point outside the image is processed as the reference does (replicated
+ * border).  The zero zone applies when both halves are >= 0 and smaller than
+ * the window's, else it is ignored; max_count is clamped to 1..100 (100 without
+ * COUNT), epsilon below 0 counts as 0.  NaN coordinates or pixels give
+ * unspecified values, never a fault or a hang.
+ * TBDK_EINVAL: win outside 1..15; an image smaller than 2*win + 5 in either
+ * dimension; criteria outside 1..3; a non-finite epsilon; an unknown pix; the
+ * pointer and pitch rules of tbdk_gftt_rois_px; nrows or row_cap below 0.
+ * nrows * row_cap == 0 is a no-op.  The call allocates nothing and uses no
+ * context scratch, so it may run on any stream.  Timed as "corner_sub_pix". */
+int tbdk_corner_sub_pix(tbdk_ctx* ctx, const void* img, int pix, int width, int height, int pitch,
+                        float* corners, const int32_t* counts, int nrows, int row_cap,
+                        const tbdk_subpix_params* params, void* stream);
+/* HOST only: the (2*win_h+1) x (2*win_w+1) window mask tbdk_corner_sub_pix uses
+ * (cornersubpix.cpp:71-93: float products of glibc expf values, zero zone
+ * applied), row-major into `mask`. */
+int tbdk_corner_sub_pix_mask(const tbdk_subpix_params* params, float* mask);
 
 /* ---- KLT box propagation ----------------------------------------------------- */
 

@@ -52,6 +52,13 @@ struct Size {
     int width = 0, height = 0;
 };
 
+// cv::TermCriteria: type is COUNT, EPS or both
+struct TermCriteria {
+    enum Type { COUNT = 1, MAX_ITER = COUNT, EPS = 2 };
+    int type = COUNT | EPS, maxCount = 20;
+    double epsilon = 0.03;
+};
+
 // Non-owning device u8 image view (GpuMat of CV_8UC1 analogue).
 struct GpuImage {
     uint8_t* data = nullptr;
@@ -612,6 +619,37 @@ private:
 };
 
 }  // namespace cuda
+
+// cv::cornerSubPix(image, corners, winSize, zeroZone, criteria) (imgproc.hpp;
+// imgproc/src/cornersubpix.cpp:44-156; the reference has no CUDA form) on the
+// device, with the CPU function's bits: corners is device memory, nrows x rowCap
+// float2 refined in place; counts (device, nrows int32, or nullptr: every row
+// full) are CornersDetector::detectRois' counts, read on the device (no host
+// sync).  A flat list of n points is nrows = 1, rowCap = n.  The defaults are
+// samples/cpp/lkdemo.cpp:85's call.  The image is a one-channel 8U, 16U or 32F view.
+inline void cornerSubPix(Context& ctx, const GpuMatView& image, float* corners, const int32_t* counts, int nrows,
+                         int rowCap, Size win = Size{10, 10}, Size zeroZone = Size{-1, -1},
+                         TermCriteria criteria = TermCriteria(), void* stream = nullptr)
+{
+    tbdk_subpix_params p{win.width, win.height, zeroZone.width, zeroZone.height, criteria.type, criteria.maxCount,
+                         criteria.epsilon};
+    check(tbdk_corner_sub_pix(ctx.get(), image.data, cuda::CornersDetector::pixOf(image, "cornerSubPix: image type"),
+                              image.width, image.height, image.pitch, corners, counts, nrows, rowCap, &p, stream),
+          "tbdk_corner_sub_pix");
+}
+// ... of a flat list of n points
+inline void cornerSubPix(Context& ctx, const GpuMatView& image, float* corners, int n, Size win = Size{10, 10},
+                         Size zeroZone = Size{-1, -1}, TermCriteria criteria = TermCriteria(), void* stream = nullptr)
+{
+    cornerSubPix(ctx, image, corners, nullptr, 1, n, win, zeroZone, criteria, stream);
+}
+// ... on a CV_8UC1 image
+inline void cornerSubPix(Context& ctx, const GpuImage& image, float* corners, int n, Size win = Size{10, 10},
+                         Size zeroZone = Size{-1, -1}, TermCriteria criteria = TermCriteria(), void* stream = nullptr)
+{
+    cornerSubPix(ctx, GpuMatView{image.data, image.width, image.height, image.pitch, DEPTH_8U, 1}, corners, nullptr, 1,
+                 n, win, zeroZone, criteria, stream);
+}
 
 namespace cuda {
 

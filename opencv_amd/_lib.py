@@ -133,6 +133,11 @@ class RansacParams(C.Structure):
     _fields_ = [("max_iters", C.c_int32), ("good_ratio", C.c_double)]
 
 
+class SubpixParams(C.Structure):
+    _fields_ = [("win_w", C.c_int32), ("win_h", C.c_int32), ("zero_w", C.c_int32), ("zero_h", C.c_int32),
+                ("criteria", C.c_int32), ("max_count", C.c_int32), ("epsilon", C.c_double)]
+
+
 class TrackerArgs(C.Structure):
     _fields_ = [("cost_of_non_assignment", C.c_double), ("time_window_size", C.c_int32),
                 ("track_age_threshold", C.c_int32), ("track_visibility_threshold", C.c_double),
@@ -259,6 +264,10 @@ SIGNATURES = {
                                     C.c_void_p]),
     "tbdk_corner_response_px": (C.c_int, [C.c_void_p, C.c_void_p, C.c_int, C.c_int, C.c_int, C.c_int, C.c_void_p,
                                           C.c_int, C.c_int, C.c_int, C.c_double, C.c_void_p]),
+    "tbdk_subpix_default_params": (C.c_int, [C.POINTER(SubpixParams)]),
+    "tbdk_corner_sub_pix": (C.c_int, [C.c_void_p, C.c_void_p, C.c_int, C.c_int, C.c_int, C.c_int, C.c_void_p,
+                                      C.c_void_p, C.c_int, C.c_int, C.POINTER(SubpixParams), C.c_void_p]),
+    "tbdk_corner_sub_pix_mask": (C.c_int, [C.POINTER(SubpixParams), C.c_void_p]),
     "tbdk_box_propagate": (C.c_int, [C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_int,
                                      C.c_int, C.c_void_p, C.c_void_p]),
     "tbdk_ransac_default_params": (C.c_int, [C.POINTER(RansacParams)]),

@@ -235,6 +235,11 @@ int tbdk_ctx_set_option(tbdk_ctx* ctx, const char* name, int64_t value)
         ctx->opt_tbd_fb_check = (int)value;
         return TBDK_OK;
     }
+    if (std::strcmp(name, "tbd_subpix") == 0) {
+        if (value < 0 || value > 15) return TBDK_EINVAL;
+        ctx->opt_tbd_subpix = (int)value;
+        return TBDK_OK;
+    }
     if (std::strcmp(name, "tbd_fit_gate") == 0) {
         ctx->opt_tbd_fit_gate = value != 0;
         return TBDK_OK;

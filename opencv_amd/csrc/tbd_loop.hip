@@ -363,6 +363,7 @@ struct tbdk_tbd {
     bool fit_flag = false;
     int fit_ransac = 0;  // ctx option tbd_fit_ransac at create: RANSAC rounds of the fit, 0 = least squares
     int fb_check = 0;    // ctx option tbd_fb_check at create: forward-backward threshold in 1/1024 px, 0 = off
+    int subpix = 0;      // ctx option tbd_subpix at create: window half size of the GFTT rows' cornerSubPix, 0 = off
     int32_t* h_flag = nullptr;
     int32_t* d_flag = nullptr;
     unsigned* d_fitcnt = nullptr;
@@ -565,6 +566,8 @@ int tbdk_tbd_create(tbdk_ctx* ctx, const tbdk_tbd_config* cfg, tbdk_tbd** out)
     if (cfg->width <= 0 || cfg->height <= 0 || cfg->max_level < 0 || !(cfg->quality_level > 0) ||
         !std::isfinite(cfg->quality_level) || !(cfg->min_distance >= 0) || !std::isfinite(cfg->min_distance))
         return TBDK_EINVAL;
+    if (ctx->opt_tbd_subpix > 0 && (cfg->width < 2 * ctx->opt_tbd_subpix + 5 || cfg->height < 2 * ctx->opt_tbd_subpix + 5))
+        return TBDK_EINVAL;  // cornerSubPix's own size rule
     tbdk_tbd* t = new (std::nothrow) tbdk_tbd();
     if (!t) return TBDK_ENOMEM;
     t->ctx = ctx;
@@ -626,6 +629,7 @@ int tbdk_tbd_create(tbdk_ctx* ctx, const tbdk_tbd_config* cfg, tbdk_tbd** out)
     t->fit_flag = t->zc && ctx->opt_tbd_fit_flag != 0;
     t->fit_ransac = ctx->opt_tbd_fit_ransac;
     t->fb_check = ctx->opt_tbd_fb_check;
+    t->subpix = ctx->opt_tbd_subpix;
     if (t->fit_flag) {
         hm(reinterpret_cast<void**>(&t->h_flag), 64);
         sm(reinterpret_cast<void**>(&t->d_flag), t->h_flag, 64);
@@ -783,6 +787,18 @@ void gather_roi(const tbdk_tbd_config& c, int x, int y, int w, int h, bool any, 
     rois.push_back(tbdk_roi{x0, y0, x1 - x0, y1 - y0});
 }
 
+// ctx option tbd_subpix: cornerSubPix over the nrows GFTT rows just launched on
+// stream s (their device counts), on the whole frame GFTT read; lkdemo's
+// criteria, no zero zone
+int refine_rows(tbdk_tbd* t, const uint8_t* img, int ipitch, int row0, int nrows, hipStream_t s)
+{
+    if (t->subpix <= 0 || nrows <= 0) return TBDK_OK;
+    const tbdk_subpix_params sp{t->subpix, t->subpix, -1, -1, 3, 20, 0.03};
+    return subpix_launch(t->ctx, img, TBDK_PIX_U8, t->cfg.width, t->cfg.height, ipitch,
+                         reinterpret_cast<float*>(t->slot_pts + (size_t)row0 * kSlotPts), t->slot_counts + row0, nrows,
+                         kSlotPts, &sp, s);
+}
+
 // one launch of the early GFTT over rois[0, n) into row set `set` from row
 // `tab0` on, over the image at img (the pinned table at h_etab[set] + tab0)
 int early_launch(tbdk_tbd* t, const tbdk_gftt_params& gp, const tbdk_roi* rois, int n, int set, int tab0,
@@ -803,6 +819,7 @@ int early_launch(tbdk_tbd* t, const tbdk_gftt_params& gp, const tbdk_roi* rois, 
     rc = gftt_launch(t->ctx, t->gftt, img, ipitch, dtab, eplan, &gp,
                      reinterpret_cast<float*>(t->slot_pts + (size_t)row0 * kSlotPts), t->slot_counts + row0, es,
                      nullptr, kSlotPts, htab, t->cmask, t->cmask_pitch);
+    if (rc == TBDK_OK) rc = refine_rows(t, img, ipitch, row0, n, es);
     if (rc != TBDK_OK) return rc;
     return map_status(hipEventRecord(t->early_done[set], es));
 }
@@ -1409,6 +1426,8 @@ int step_impl(tbdk_tbd* t, const uint8_t* frame, int pitch, int frame_id, const 
         rc = gftt_launch(t->ctx, t->gftt2, L0.data + (size_t)L0.pad * L0.pitch + L0.pad, L0.pitch, t->d_tab, plan, &gp,
                          reinterpret_cast<float*>(t->slot_pts + (size_t)prow0 * kSlotPts), t->slot_counts + prow0,
                          t->side, next ? t->eig_done : nullptr, kSlotPts, t->h_tab, t->cmask, t->cmask_pitch);
+        if (rc == TBDK_OK)
+            rc = refine_rows(t, L0.data + (size_t)L0.pad * L0.pitch + L0.pad, L0.pitch, prow0, nroi, t->side);
         if (rc != TBDK_OK) return rc;
     }
     // post_done also after an early GFTT none of whose ROIs was used: the next

@@ -107,6 +107,7 @@ struct tbdk_ctx {
     int opt_tbd_fit_gate = 1;    // tbdk_ctx_set_option("tbd_fit_gate"): the host launches the fit once the look-ahead PyrLK is done
     int opt_tbd_fit_ransac = 0;  // tbdk_ctx_set_option("tbd_fit_ransac"): RANSAC rounds of the loop's fit, 0 = least squares (read by tbdk_tbd_create)
     int opt_tbd_fb_check = 0;    // tbdk_ctx_set_option("tbd_fb_check"): the loop's forward-backward check, threshold in 1/1024 px, 0 = off (read by tbdk_tbd_create)
+    int opt_tbd_subpix = 0;      // tbdk_ctx_set_option("tbd_subpix"): the loop refines its GFTT corners, window half size, 0 = off (read by tbdk_tbd_create)
     std::string timing_only;  // ",name,name," filter of tbdk_timing_select ("" = all)
     int timing_every = 1;     // tbdk_ctx_set_option("timing_every"): events on every Nth selected launch
     std::vector<std::pair<std::string, int64_t>> timing_calls;  // selected launches per name (sampled or not)
@@ -446,4 +447,7 @@ hipError_t launch_gftt_resp(const GfttRespArgs& a, int ncblk, int max_w, int max
                             int pix = TBDK_PIX_U8);
 int gftt_reserve_resp(GfttScratch& sc, int device, int64_t max_px);
 inline bool gftt_generic(const tbdk_gftt_params* p) { return p->block_size != 3 || p->use_harris != 0; }
+// ---- klt_subpix.hip: tbdk_corner_sub_pix on a HIP stream (one launch, no scratch) ----
+int subpix_launch(tbdk_ctx* ctx, const void* img, int pix, int width, int height, int pitch, float* corners,
+                  const int32_t* counts, int nrows, int row_cap, const tbdk_subpix_params* p, hipStream_t s);
 }  // namespace tbdk

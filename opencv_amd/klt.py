@@ -718,6 +718,53 @@ class GoodFeaturesToTrackDetector:
         return c[0, :k]
 
 
+def subpix_params(win=(10, 10), zero_zone=(-1, -1), criteria=(3, 20, 0.03)) -> _lib.SubpixParams:
+    """tbdk_subpix_params of cv::cornerSubPix's (winSize, zeroZone, TermCriteria(type, maxCount, epsilon))"""
+    return _lib.SubpixParams(int(win[0]), int(win[1]), int(zero_zone[0]), int(zero_zone[1]), int(criteria[0]),
+                             int(criteria[1]), float(criteria[2]))
+
+
+def corner_sub_pix_mask(win=(10, 10), zero_zone=(-1, -1)) -> np.ndarray:
+    """The (2*win_h+1, 2*win_w+1) float32 window mask corner_sub_pix uses
+    (tbdk_corner_sub_pix_mask; host only, needs no GPU)."""
+    prm = subpix_params(win, zero_zone)
+    out = np.zeros((2 * prm.win_h + 1, 2 * prm.win_w + 1), np.float32)
+    if not (1 <= prm.win_w <= 15 and 1 <= prm.win_h <= 15):
+        raise _lib.TbdkError("corner_sub_pix_mask: win must be 1..15")
+    _lib.check(_lib.load().tbdk_corner_sub_pix_mask(C.byref(prm), out.ctypes.data_as(C.c_void_p)),
+               "tbdk_corner_sub_pix_mask")
+    return out
+
+
+def corner_sub_pix(image: torch.Tensor, corners: torch.Tensor, win=(10, 10), zero_zone=(-1, -1),
+                   criteria=(3, 20, 0.03), counts: torch.Tensor | None = None, ctx: Context | None = None,
+                   stream=None) -> torch.Tensor:
+    """cv::cornerSubPix(image, corners, win, zero_zone, TermCriteria(*criteria))
+    (imgproc/src/cornersubpix.cpp:44-156; the defaults are samples/cpp/lkdemo.cpp:85's),
+    on the device, bit-exact with the CPU function (tbdk_corner_sub_pix).
+    image: 2-D uint8, uint16 or float32 device tensor with stride(1) == 1 (uint16:
+    the float32 result of the same values).  corners: float32 device tensor (n, 2),
+    or (rows, cap, 2) with counts (rows,) int32 as detect_rois returns them: row
+    r's first counts[r] points are refined (counts None: all of them).  Returns a
+    refined copy; the input is not modified."""
+    pix, pitch = _corner_image(image, "corner_sub_pix")
+    if not isinstance(corners, torch.Tensor) or corners.dtype != torch.float32 or corners.device != image.device or \
+            corners.dim() not in (2, 3) or corners.shape[-1] != 2:
+        raise _lib.TbdkError("corner_sub_pix: corners must be a float32 (n, 2) or (rows, cap, 2) tensor on the image's device")
+    rows, cap = (1, corners.shape[0]) if corners.dim() == 2 else corners.shape[:2]
+    if counts is not None and (not isinstance(counts, torch.Tensor) or counts.dtype != torch.int32 or
+                               counts.device != image.device or counts.shape != (rows,) or not counts.is_contiguous()):
+        raise _lib.TbdkError("corner_sub_pix: counts must be a contiguous int32 (rows,) tensor on the image's device")
+    ctx = ctx or Context.get(image.device.index or 0)
+    out = corners.clone(memory_format=torch.contiguous_format)
+    prm = subpix_params(win, zero_zone, criteria)
+    _lib.check(ctx.lib.tbdk_corner_sub_pix(
+        ctx.handle, C.c_void_p(image.data_ptr()), pix, image.shape[1], image.shape[0], pitch,
+        C.c_void_p(out.data_ptr()), C.c_void_p(counts.data_ptr()) if counts is not None else None, int(rows),
+        int(cap), C.byref(prm), _stream_ptr(stream)), "tbdk_corner_sub_pix")
+    return out
+
+
 def hbm_copy(dst: torch.Tensor, src: torch.Tensor, ctx: Context | None = None, stream=None):
     """dst <- src (contiguous device tensors of equal byte size, a multiple of
     16) through libtbdk's 16-byte-per-lane stream-copy kernel (tbdk_hbm_copy;

@@ -3,7 +3,8 @@
 goodFeaturesToTrack, cornerMinEigenVal / cornerHarris, warpAffine,
 calcOpticalFlowFarneback, HOGDescriptor) on the cases of tests/_reference_cases.py
 (goodFeaturesToTrack under a mask: tests/_gftt_mask_cases.py; the corner maps and
-goodFeaturesToTrack on CV_32F images: tests/_gftt_f32_cases.py)
+goodFeaturesToTrack on CV_32F images: tests/_gftt_f32_cases.py; cornerSubPix:
+tests/_subpix_cases.py)
 into tests/golden/reference_<op>.npz, through tools/reference_driver.cpp (how to
 build it: tools/record_reference_cases.md).
 
@@ -38,12 +39,13 @@ import _oracle as O  # noqa: E402
 import _reference_cases as RC  # noqa: E402
 import _gftt_mask_cases as MC  # noqa: E402
 import _gftt_f32_cases as FC  # noqa: E402
+import _subpix_cases as SC  # noqa: E402
 
 LIMIT = 256 * 1024
 STATES = ("default", "noavx2")
 # the state each oracle file models where the two differ (README, numerics)
 MODELLED = {"pyramid": "both", "pyrlk": "both", "warpaffine": "both", "gftt": "noavx2", "gftt_mask": "noavx2",
-            "cornermaps": "noavx2", "gftt_f32": "noavx2",
+            "cornermaps": "noavx2", "gftt_f32": "noavx2", "subpix": "both",
             "farneback": "noavx2", "farneback_box": "noavx2", "hog": "default"}
 
 
@@ -215,6 +217,33 @@ def rec_gftt_f32(d):
     return cases, dict(nmaps=np.array(len(FC.map_cases()), np.int32))
 
 
+def rec_subpix(d):
+    """cornerSubPix (tests/_subpix_cases.py): per image its point set (the 8-bit
+    image's goodFeaturesToTrack corners, moved copies, special points), stored in
+    the fixture; per case the refined points; and the driver's expf table"""
+    extra = {}
+    for name, _, _, _ in SC.IMAGES:
+        img = SC.image(name)
+        _, rd = d.run("gftt", dict(a=img), **img_kw(img), maxc=SC.GFTT[0], ql=SC.GFTT[1], md=SC.GFTT[2], block=3,
+                      harris=0, k=0.04)
+        extra[f"pts_{name}"] = SC.points(name, rd("c", np.float32).reshape(-1, 2))
+    cases = []
+    for name, depth, win, zero, crit in SC.cases():
+        img, pts = SC.image(name, depth), extra[f"pts_{name}"]
+        out, rd = d.run("subpix", dict(a=img, pts=pts), w=img.shape[1], h=img.shape[0], depth=depth, n=len(pts),
+                        winw=win[0], winh=win[1], zw=zero[0], zh=zero[1], ctype=crit[0], cmax=crit[1],
+                        ceps=float(crit[2]))
+        cases.append(({}, dict(c=rd("c", np.float32).reshape(-1, 2))))
+        table = np.zeros((15, 16), np.float32)
+        for line in out:
+            f = line.split()
+            assert f[0] == "expf" and len(f) == int(f[1]) + 3, line
+            table[int(f[1]) - 1, :len(f) - 2] = np.array([int(b, 16) for b in f[2:]], np.uint32).view(np.float32)
+        assert "expf" not in extra or np.array_equal(extra["expf"].view(np.uint32), table.view(np.uint32))
+        extra["expf"] = table
+    return cases, extra
+
+
 def warp_table():
     """(flags, border, bval, sw, sh, dw, dh, M) per case: 4 interpolations x 6 borders x
     the inverse flag on matrices drawn from a fixed seed, then the degenerate matrices"""
@@ -346,13 +375,13 @@ def merge(op, rec, whole_limit):
 
 
 RECORDERS = {"pyramid": rec_pyramid, "pyrlk": rec_pyrlk, "gftt": rec_gftt, "gftt_mask": rec_gftt_mask,
-             "cornermaps": rec_cornermaps, "gftt_f32": rec_gftt_f32,
+             "cornermaps": rec_cornermaps, "gftt_f32": rec_gftt_f32, "subpix": rec_subpix,
              "warpaffine": rec_warpaffine, "farneback": rec_farneback, "farneback_box": rec_farneback_box,
              "hog": rec_hog}
 # bytes up to which an output is stored whole (tests/_reference_cases.py: WHOLE_LIMIT).  The kernels are
 # compared with the box Farneback flows within a tolerance, so all six stay whole (about 7 KB under LIMIT)
 WHOLE = {"farneback": 20480, "farneback_box": 72800, "pyrlk": 1 << 20, "gftt": 1 << 20, "gftt_mask": 1 << 20,
-         "hog": 16384}
+         "hog": 16384, "subpix": 1 << 20}
 # (gftt_f32: maps above RC.WHOLE_LIMIT as row CRCs; its corner lists are far below it)
 
 
@@ -383,6 +412,8 @@ def case_label(op, i):
             return f"{kind} {h}x{w} block {block} " + ("harris" if harris else "minEigenVal")
         kind, r, mk, maxc, ql, md, block, harris = FC.list_cases()[i - nm]
         return f"{kind} roi {r} mask {mk} ({maxc}, {ql}, {md}) block {block}" + (" harris" if harris else "")
+    if op == "subpix":
+        return SC.label(i)
     if op == "cornermaps":
         w, h, _ = RC.CMAP_SHAPES[i // len(RC.CMAP_MODES)]
         block, harris = RC.CMAP_MODES[i % len(RC.CMAP_MODES)]

@@ -16,12 +16,16 @@
 //   gftt  a= w= h= maxc= ql= md= block= harris= k= [mask=] [depth=8u|32f] -> c (f32 pairs); prints the count
 //                                                  (mask: raw u8, w x h, goodFeaturesToTrack's mask)
 //   cmap  a= w= h= block= harris= k= [depth=8u|32f] -> e (f32): cornerMinEigenVal / cornerHarris, ksize 3
+//   subpix a= w= h= [depth=8u|32f] pts= n= winw= winh= zw= zh= ctype= cmax= ceps= -> c (f32 pairs): cornerSubPix;
+//                                                  prints "expf w bits..." for w = 1..15: expf(-(k/w)^2), k = 0..w
 //   warp  a= w= h= m= (6 doubles, raw) dst= dw= dh= flags= border= bval=   -> w (u8)
 //   fb    a= b= w= h= ps= lv= ws= it= pn= sg= flags= [init=]               -> f (f32 pairs)
 //   hoggrad a= w= h= cn= gamma= signed=            -> g (f32 pairs), qa (u8 pairs)
 //   hogdet  a= w= h= cn= win=64|48 hit= group=     -> loc (i32 pairs), wt (f64), r (i32 x4), rw (f64), svm (f32)
+#include <cmath>
 #include <cstdio>
 #include <cstdlib>
+#include <cstring>
 #include <map>
 #include <stdexcept>
 #include <string>
@@ -86,7 +90,7 @@ static Mat image_depth(const std::string& key, int w, int h)
 static int run(const std::string& op, const std::string& out)
 {
     const int w = iarg("w"), h = iarg("h"), cn = has("cn") ? iarg("cn") : 1;
-    Mat a = op == "gftt" || op == "cmap" ? image_depth("a", w, h) : image("a", w, h, cn);
+    Mat a = op == "gftt" || op == "cmap" || op == "subpix" ? image_depth("a", w, h) : image("a", w, h, cn);
     if (op == "pyr") {
         std::vector<Mat> pyr;
         int top = buildOpticalFlowPyramid(a, pyr, Size(iarg("winw"), iarg("winh")), iarg("maxl"), true);
@@ -133,6 +137,24 @@ static int run(const std::string& op, const std::string& out)
         else
             cornerMinEigenVal(a, e, iarg("block"), 3);
         wr(out, "e", e);
+    } else if (op == "subpix") {
+        const int n = iarg("n");
+        std::vector<Point2f> c(n);
+        rd(arg("pts"), c.data(), sizeof(Point2f) * n);
+        cornerSubPix(a, c, Size(iarg("winw"), iarg("winh")), Size(iarg("zw"), iarg("zh")),
+                     TermCriteria(iarg("ctype"), iarg("cmax"), darg("ceps")));
+        wr(out, "c", c.data(), sizeof(Point2f) * n);
+        // the window mask's exponentials, expf(-(k/w)^2), as float bits: one line per w = 1..15, k = 0..w
+        for (int ww = 1; ww <= 15; ++ww) {
+            std::printf("expf %d", ww);
+            for (int k = 0; k <= ww; ++k) {
+                const float x = (float)k / ww, e = expf(-x * x);
+                unsigned bits;
+                std::memcpy(&bits, &e, 4);
+                std::printf(" %08x", bits);
+            }
+            std::printf("\n");
+        }
     } else if (op == "warp") {
         double m[6];
         rd(arg("m"), m, sizeof m);
