@@ -108,6 +108,10 @@ int tbdk_ctx_destroy(tbdk_ctx* ctx);
  *       eigenvalue strips as a fresh-start mismatch, forcing the re-walk
  *       rounds taken when a segment's fresh start differs from the
  *       reference's running box-filter sum (results equal).
+ *   "gftt_wide" (0/1, default 0): 0: tbdk_gftt_rois* select a ROI's corners in
+ *       one workgroup's LDS where its candidates and accepted corners fit, and
+ *       by the wide path (candidates and accepted state in global scratch)
+ *       where they do not; 1: every ROI by the wide path (results equal).
  *   "pyr_fuse" (0/1, default 1): tbdk_pyr_build of a u8 pyramid: 1
  *       computes level 0's padded copy and level 1 in one launch, then one
  *       launch per level; 0: one launch per level
@@ -471,11 +475,21 @@ typedef struct tbdk_gftt_params {
  *   img        : device u8 image (width x height, row pitch in bytes)
  *   rois       : HOST array of nroi ROIs (copied during the call)
  *   corners    : device, nroi x max_corners x float2, frame coordinates
- *   counts     : device, nroi int32 (corners found; -1 if a ROI produced more
- *                candidates than the on-chip buffer holds — never truncated)
- * Scratch grows on demand (tbdk_gftt_reserve avoids allocation in the call);
- * it is the context's: calls on one context from different streams must be
- * ordered by the caller (a TBD loop has scratch of its own). */
+ *   counts     : device, nroi int32: corners found, never negative here.  Any
+ *                ROI size up to the whole frame and any max_corners: a ROI with
+ *                more candidates than the on-chip buffer holds (16384 at most,
+ *                fewer for a large max_corners), or with an accepted list that
+ *                does not fit there, is selected by the wide path in global
+ *                scratch, with the same corners (option "gftt_wide"; timing name
+ *                "gftt_wide" for its launches, beside "gftt").  The value -1
+ *                (candidate overflow, never a truncated list) stays reserved:
+ *                the TBD loop's own GFTT still reports it, and
+ *                tbdk_corner_sub_pix leaves such rows untouched.
+ * Scratch grows on demand (tbdk_gftt_reserve avoids allocation in the call: it
+ * covers the wide path too, 20 more bytes per ROI pixel, which a call otherwise
+ * allocates when it first routes a ROI there); it is the context's: calls on
+ * one context from different streams must be ordered by the caller (a TBD
+ * loop has scratch of its own). */
 int tbdk_gftt_rois(tbdk_ctx* ctx, const uint8_t* img, int width, int height, int pitch,
                    const tbdk_roi* rois, int nroi, const tbdk_gftt_params* params,
                    float* corners, int32_t* counts, void* stream);
@@ -497,8 +511,8 @@ int tbdk_gftt_rois(tbdk_ctx* ctx, const uint8_t* img, int width, int height, int
  *     response still suppresses a masked-in pixel;
  *   - a candidate is an interior pixel with val != 0, val == dilated and a
  *     non-zero mask byte; sort, min-distance walk and max_corners as unmasked;
- *   - counts[i] = -1 only when the candidates that pass the mask exceed the
- *     on-chip capacity.
+ *   - when the candidates that pass the mask exceed the on-chip capacity the
+ *     ROI goes through the wide path, as in tbdk_gftt_rois.
  * So the corners differ from those of an unmasked call filtered by the mask.
  * TBDK_EINVAL for mask != NULL && mask_pitch < width. */
 int tbdk_gftt_rois_masked(tbdk_ctx* ctx, const uint8_t* img, int width, int height, int pitch,
@@ -550,7 +564,7 @@ int tbdk_gftt_reserve(tbdk_ctx* ctx, int max_rois, int64_t max_total_pixels);
  * walk's row segments rarely start on the reference's running sum; they are
  * then walked again in the reference's order, so the result stays exact and
  * the call takes up to a few times longer.
- * mask NULL: unmasked.  Scratch, counts == -1 on candidate overflow, the
+ * mask NULL: unmasked.  Scratch, the wide path for large ROIs, the
  * "gftt_compact" / "gftt_eig_redo" options and the timing names are those of
  * the 8-bit entries.
  * TBDK_EINVAL: an unknown pix; an F32 img pointer or pitch that is not a

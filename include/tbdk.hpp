@@ -389,8 +389,10 @@ public:
             new CornersDetector(ctx, maxCorners, qualityLevel, minDistance, blockSize, useHarrisDetector, harrisK));
     }
 
-    // corners: device, maxCorners float2; count: device int32 (corners found, -1 on
-    // candidate overflow).  The count stays on the device (no host sync).
+    // corners: device, maxCorners float2; count: device int32, the corners found
+    // (never negative: a frame of any size and any maxCorners is served, the large
+    // ones by the wide selection path of tbdk_gftt_rois).  The count stays on the
+    // device (no host sync).
     void detect(const GpuImage& image, float* corners, int32_t* count, void* stream = nullptr)
     {
         tbdk_roi r{0, 0, image.width, image.height};

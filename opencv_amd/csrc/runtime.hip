@@ -163,6 +163,11 @@ int tbdk_ctx_set_option(tbdk_ctx* ctx, const char* name, int64_t value)
         ctx->opt_gftt_eig_redo = value != 0;
         return TBDK_OK;
     }
+    if (std::strcmp(name, "gftt_wide") == 0) {
+        if (value < 0 || value > 1) return TBDK_EINVAL;
+        ctx->opt_gftt_wide = (int)value;
+        return TBDK_OK;
+    }
     if (std::strcmp(name, "timing_every") == 0) {
         if (value < 1 || value > (1 << 20)) return TBDK_EINVAL;
         ctx->timing_every = (int)value;
@@ -811,6 +816,9 @@ int gftt_prepare(const tbdk_roi* rois, int nroi, int width, int height, const tb
         ncblk += strips;
         if (r.width >= 3 && r.height >= 3) words += strips * r.height;  // smaller ROIs have no interior
         max_area = std::max(max_area, r.width * r.height);
+        const int interior = r.width >= 3 && r.height >= 3 ? (r.width - 2) * (r.height - 2) : 0;
+        plan->max_interior = std::max(plan->max_interior, interior);
+        plan->min_interior = i == 0 ? interior : std::min(plan->min_interior, interior);
         plan->max_w = std::max(plan->max_w, r.width);
         plan->max_h = std::max(plan->max_h, r.height);
     }
@@ -851,13 +859,70 @@ static void gftt_resp_args(GfttRespArgs& ra, const GfttScratch& sc, const uint8_
 
 void gftt_scratch_free(GfttScratch& sc)
 {
-    for (void** p : {&sc.rois, reinterpret_cast<void**>(&sc.blk), &sc.planes, &sc.cand, &sc.resp}) {
+    for (void** p : {&sc.rois, reinterpret_cast<void**>(&sc.blk), &sc.planes, &sc.cand, &sc.resp, &sc.wide_keys,
+                     &sc.wide_cells, &sc.wide_state}) {
         if (*p) (void)hipFree(*p);
         *p = nullptr;
     }
     sc.cap_rois = 0;
     sc.cap_px = 0;
     sc.cap_resp_px = 0;
+    sc.cap_wide_rois = 0;
+    sc.cap_wide_px = 0;
+}
+
+// The wide walk's distance-test geometry.  rad: the largest |d| with d^2 <
+// min_distance^2, as gftt_select_kernel derives it.  cell: the largest s with
+// 2 (s - 1)^2 < min_distance^2, so that any two pixels of a cell are closer than
+// min_distance and a cell holds at most one accepted corner; then rad < 2 s and
+// a candidate's window touches at most 5 x 5 cells.  A ROI side is at most
+// 65535, so beyond hypot(65535, 65535) every distance is closer and the grid is
+// one cell: the geometry is taken from the clamped value (the test itself keeps
+// min_distance as given, infinite included), and the loops below are bounded.
+void gftt_wide_geometry(double min_distance, int* rad, int* cell)
+{
+    *rad = -1;  // no distance test: min_distance < 1 (NaN included)
+    *cell = 1;
+    if (!(min_distance >= 1.0)) return;
+    const double md = std::min(min_distance, 92682.0), md2 = md * md;
+    int r = (int)std::ceil(md) - 1;
+    if ((double)(r + 1) * (r + 1) < md2) r++;
+    int s = std::max(1, (int)(md * 0.70710678118654752));
+    while (2.0 * (double)s * (double)s < md2) s++;                            // now 2 s^2 >= md2: rad < 2 s
+    while (s > 1 && !(2.0 * (double)(s - 1) * (double)(s - 1) < md2)) s--;    // and 2 (s-1)^2 < md2
+    *rad = r;
+    *cell = s;
+}
+
+// the wide path's buffers: 2 x 8 B of keys (as gathered, and partitioned) and 4 B
+// of cells per ROI pixel (every interior pixel can be a candidate, every pixel
+// a cell), 16 B of state per ROI
+int gftt_reserve_wide(GfttScratch& sc, int device, int max_rois, int64_t max_px)
+{
+    if (max_rois < 0 || max_px < 0) return TBDK_EINVAL;
+    if (max_rois <= sc.cap_wide_rois && max_px <= sc.cap_wide_px) return TBDK_OK;
+    DeviceGuard g(device);
+    const int rois = std::max(max_rois, sc.cap_wide_rois);
+    const int64_t px = std::max(max_px, sc.cap_wide_px);
+    for (void** p : {&sc.wide_keys, &sc.wide_cells, &sc.wide_state}) {
+        if (*p) (void)hipFree(*p);  // waits for the device: no launch still reads it
+        *p = nullptr;
+    }
+    sc.cap_wide_rois = 0;
+    sc.cap_wide_px = 0;
+    hipError_t e = hipMalloc(&sc.wide_keys, 2 * sizeof(uint64_t) * (size_t)std::max<int64_t>(px, 1));
+    if (e == hipSuccess) e = hipMalloc(&sc.wide_cells, sizeof(uint32_t) * (size_t)std::max<int64_t>(px, 1));
+    if (e == hipSuccess) e = hipMalloc(&sc.wide_state, sizeof(GfttWideState) * (size_t)std::max(rois, 1));
+    if (e != hipSuccess) {
+        for (void** p : {&sc.wide_keys, &sc.wide_cells, &sc.wide_state}) {
+            if (*p) (void)hipFree(*p);
+            *p = nullptr;
+        }
+        return map_err(e);
+    }
+    sc.cap_wide_rois = rois;
+    sc.cap_wide_px = px;
+    return TBDK_OK;
 }
 
 int gftt_reserve_resp(GfttScratch& sc, int device, int64_t max_px)
@@ -898,7 +963,7 @@ int gftt_reserve(GfttScratch& sc, int device, int max_rois, int64_t max_px)
 int gftt_launch(tbdk_ctx* ctx, GfttScratch& sc, const uint8_t* img, int pitch, const GfttRoi* d_rois,
                 const GfttPlan& plan, const tbdk_gftt_params* p, float* corners, int32_t* counts, hipStream_t s,
                 hipEvent_t after_eig, int corner_stride, const GfttRoi* h_rois, const uint8_t* mask, int mask_pitch,
-                int pix)
+                int pix, bool wide_ok)
 {
     if (corner_stride != 0 && corner_stride < p->max_corners) return TBDK_EINVAL;
     int rc = gftt_reserve(sc, ctx->device, plan.nroi, plan.total);
@@ -937,9 +1002,23 @@ int gftt_launch(tbdk_ctx* ctx, GfttScratch& sc, const uint8_t* img, int pitch, c
         if (fits) a.ninl = plan.nroi;
     }
     gftt_plan(a, plan.max_area);
+    // Routing (whole-frame GFTT).  A ROI can overflow when it has more
+    // interior pixels than the planned LDS capacity has keys.  lds: the LDS
+    // select runs.  wide: the wide stage follows it for the ROIs that report
+    // overflow (counts -1), or takes every ROI when the LDS select does not run:
+    // its accepted list does not fit LDS at all, every ROI of the call can
+    // overflow (a whole frame), or ctx option gftt_wide = 1.  A call none of
+    // whose ROIs can overflow launches what it always did.
+    const bool lds_fits = (long)gftt_select_smem(a.cap, a.max_corners, a.img_bytes) <= kGfttSelectLds;
+    const bool lds = !wide_ok || (lds_fits && !ctx->opt_gftt_wide && plan.min_interior <= a.cap);
+    const bool wide = wide_ok && (!lds || plan.max_interior > a.cap);
+    if (wide) {
+        rc = gftt_reserve_wide(sc, ctx->device, plan.nroi, plan.total);
+        if (rc != TBDK_OK) return rc;
+    }
     hipError_t e;
     if (!gftt_generic(p)) {
-        e = launch_gftt(a, s, after_eig, pix);
+        e = launch_gftt(a, s, after_eig, pix, lds);
     } else {
         rc = gftt_reserve_resp(sc, ctx->device, plan.total);
         if (rc != TBDK_OK) return rc;
@@ -948,9 +1027,21 @@ int gftt_launch(tbdk_ctx* ctx, GfttScratch& sc, const uint8_t* img, int pitch, c
                        a.mask_pitch, pix);
         e = launch_gftt_resp(ra, plan.ncblk, plan.max_w, plan.max_h, plan.max_area, s, pix);
         if (e == hipSuccess && after_eig) e = hipEventRecord(after_eig, s);
-        if (e == hipSuccess) e = launch_gftt_select(a, s);
+        if (e == hipSuccess && lds) e = launch_gftt_select(a, s);
     }
     timing_end(ctx, rec, s);
+    if (e == hipSuccess && wide) {
+        rec = timing_begin(ctx, "gftt_wide", s);
+        GfttWide w;
+        w.keys = static_cast<uint64_t*>(sc.wide_keys);
+        w.keys2 = w.keys + std::max<int64_t>(sc.cap_wide_px, 1);
+        w.cells = static_cast<uint32_t*>(sc.wide_cells);
+        w.state = static_cast<GfttWideState*>(sc.wide_state);
+        w.all = lds ? 0 : 1;
+        gftt_wide_geometry(p->min_distance, &w.rad, &w.cell);
+        e = launch_gftt_wide(a, w, s);
+        timing_end(ctx, rec, s);
+    }
     return map_err(e);
 }
 
@@ -961,7 +1052,9 @@ extern "C" {
 int tbdk_gftt_reserve(tbdk_ctx* ctx, int max_rois, int64_t max_total_pixels)
 {
     if (!ctx || max_rois < 0 || max_total_pixels < 0) return TBDK_EINVAL;
-    return gftt_reserve(ctx->gftt, ctx->device, max_rois, max_total_pixels);
+    const int rc = gftt_reserve(ctx->gftt, ctx->device, max_rois, max_total_pixels);
+    if (rc != TBDK_OK) return rc;
+    return gftt_reserve_wide(ctx->gftt, ctx->device, max_rois, max_total_pixels);
 }
 
 int tbdk_gftt_rois(tbdk_ctx* ctx, const uint8_t* img, int width, int height, int pitch, const tbdk_roi* rois,
@@ -1002,7 +1095,7 @@ int tbdk_gftt_rois_px(tbdk_ctx* ctx, const void* img_, int pix, int width, int h
     std::vector<GfttRoi> tab((size_t)nroi);
     int rc = gftt_prepare(rois, nroi, width, height, p, tab.data(), &plan);
     if (rc != TBDK_OK) return rc;
-    rc = tbdk_gftt_reserve(ctx, nroi, plan.total);
+    rc = gftt_reserve(ctx->gftt, ctx->device, nroi, plan.total);  // the wide path's buffers: gftt_launch, when it routes there
     if (rc != TBDK_OK) return rc;
     DeviceGuard g(ctx->device);
     hipStream_t s = static_cast<hipStream_t>(stream);
@@ -1010,7 +1103,7 @@ int tbdk_gftt_rois_px(tbdk_ctx* ctx, const void* img_, int pix, int width, int h
     hipError_t e = hipMemcpyAsync(ctx->gftt.rois, tab.data(), sizeof(GfttRoi) * (size_t)nroi, hipMemcpyHostToDevice, s);
     if (e != hipSuccess) return map_err(e);
     return gftt_launch(ctx, ctx->gftt, img, pitch, static_cast<const GfttRoi*>(ctx->gftt.rois), plan, p, corners,
-                       counts, s, nullptr, 0, tab.data(), mask, mask_pitch, pix);
+                       counts, s, nullptr, 0, tab.data(), mask, mask_pitch, pix, true);
 }
 
 static int corner_min_eig_px(tbdk_ctx* ctx, const uint8_t* img, int pix, int width, int height, int pitch, float* dst,

@@ -65,6 +65,12 @@ struct GfttScratch {
     int cap_rois = 0;
     int64_t cap_px = 0;
     int64_t cap_resp_px = 0;
+    // the wide selection path (klt_gftt_wide.hip), allocated when a call first needs it
+    void* wide_keys = nullptr;   // 2 x cap_wide_px uint64 candidate keys: as gathered, and partitioned
+    void* wide_cells = nullptr;  // cap_wide_px uint32 cells of the walk's grid
+    void* wide_state = nullptr;  // GfttWideState[cap_wide_rois]
+    int cap_wide_rois = 0;
+    int64_t cap_wide_px = 0;
 };
 struct HogScratch;  // hog.hip
 struct FrontScratch;  // frontend.hip
@@ -108,6 +114,7 @@ struct tbdk_ctx {
     int opt_tbd_fit_ransac = 0;  // tbdk_ctx_set_option("tbd_fit_ransac"): RANSAC rounds of the loop's fit, 0 = least squares (read by tbdk_tbd_create)
     int opt_tbd_fb_check = 0;    // tbdk_ctx_set_option("tbd_fb_check"): the loop's forward-backward check, threshold in 1/1024 px, 0 = off (read by tbdk_tbd_create)
     int opt_tbd_subpix = 0;      // tbdk_ctx_set_option("tbd_subpix"): the loop refines its GFTT corners, window half size, 0 = off (read by tbdk_tbd_create)
+    int opt_gftt_wide = 0;       // tbdk_ctx_set_option("gftt_wide"): 0 = the wide selection where the LDS one cannot serve, 1 = for every ROI
     std::string timing_only;  // ",name,name," filter of tbdk_timing_select ("" = all)
     int timing_every = 1;     // tbdk_ctx_set_option("timing_every"): events on every Nth selected launch
     std::vector<std::pair<std::string, int64_t>> timing_calls;  // selected launches per name (sampled or not)
@@ -400,6 +407,8 @@ size_t gftt_select_smem(int cap, int max_corners, int img_bytes);
 void gftt_plan(GfttArgs& a, int max_area);  // sets cap and img_bytes
 struct GfttPlan {
     int nroi = 0, ncblk = 0, max_area = 0, max_w = 0, max_h = 0;
+    int max_interior = 0;  // most interior pixels ((w - 2) (h - 2)) of a ROI: its most candidates
+    int min_interior = 0;  // ... and the fewest
     int64_t total = 0;  // ROI pixels
     int64_t words = 0;  // local-maximum words
 };
@@ -413,16 +422,45 @@ int gftt_reserve(GfttScratch& sc, int device, int max_rois, int64_t max_px);
 void gftt_scratch_free(GfttScratch& sc);
 // h_rois (optional): a host-readable copy of the table, carried in the kernel
 // arguments when it fits (ctx option gftt_inline)
+// wide_ok: ROIs the LDS select cannot serve go through the wide path (the
+// standalone entry points); false: they report counts -1 (the TBD loop)
 int gftt_launch(tbdk_ctx* ctx, GfttScratch& sc, const uint8_t* img, int pitch, const GfttRoi* d_rois, const GfttPlan& plan,
                 const tbdk_gftt_params* p, float* corners, int32_t* counts, hipStream_t s,
                 hipEvent_t after_eig = nullptr, int corner_stride = 0,  // 0: max_corners
                 const GfttRoi* h_rois = nullptr, const uint8_t* mask = nullptr, int mask_pitch = 0,
-                int pix = TBDK_PIX_U8);
+                int pix = TBDK_PIX_U8, bool wide_ok = false);
 // pix (TBDK_PIX_*): the pixel type of a.img, a.pitch in bytes; the 16U / 32F
 // launches are kernel instances of their own, the arguments are the same
-hipError_t launch_gftt(const GfttArgs& a, hipStream_t s, hipEvent_t after_eig = nullptr, int pix = TBDK_PIX_U8);
+// select: false leaves the LDS select out (a call routed to the wide path as a whole)
+hipError_t launch_gftt(const GfttArgs& a, hipStream_t s, hipEvent_t after_eig = nullptr, int pix = TBDK_PIX_U8,
+                       bool select = true);
 hipError_t launch_gftt_eig(const GfttArgs& a, hipStream_t s, int pix = TBDK_PIX_U8);  // eigenvalue planes only
 hipError_t launch_gftt_select(const GfttArgs& a, hipStream_t s);
+// ---- the wide selection path (klt_gftt_wide.hip): ROIs whose candidates or accepted
+// corners do not fit gftt_select_kernel's LDS, candidates and accepted state in global scratch
+struct GfttWideState {  // per ROI, cleared before the gather launch
+    int total;          // candidates gathered
+    float thr, vmax;    // threshold and ROI maximum: thr < every candidate's value <= vmax
+    int pad;
+};
+struct GfttWide {
+    uint64_t* keys;        // per ROI at GfttRoi::off: its candidates' keys (<= interior pixels)
+    uint64_t* keys2;       // ... and the same keys partitioned into buckets (ROIs of more keys than one chunk)
+    uint32_t* cells;       // per ROI at GfttRoi::off: the walk's cell grid (<= one cell per pixel)
+    GfttWideState* state;  // nroi
+    int all;               // != 0: every ROI (the LDS select did not run); 0: those with counts[r] == -1
+    // the walk's distance-test geometry (gftt_wide_geometry, on the host): pixels
+    // with |dx|, |dy| <= rad can be closer than min_distance (-1: no distance test,
+    // min_distance < 1); cell: the grid's cell side
+    int rad, cell;
+};
+void gftt_wide_geometry(double min_distance, int* rad, int* cell);
+constexpr int kWideParts = 64;  // gather workgroups per ROI
+// scratch of the wide path for max_rois ROIs of max_px pixels in total (grows only)
+int gftt_reserve_wide(GfttScratch& sc, int device, int max_rois, int64_t max_px);
+hipError_t launch_gftt_wide(const GfttArgs& a, const GfttWide& w, hipStream_t s);
+// the largest dynamic LDS gftt_select_kernel can be given
+constexpr long kGfttSelectLds = 160L * 1024 - 2048;
 // blockSize != 3 or Harris (klt_gftt_resp.hip): the response plane, strip
 // maxima and local-maximum words in gftt_eig_kernel's layout
 struct GfttRespArgs {

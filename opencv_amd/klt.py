@@ -675,6 +675,10 @@ class GoodFeaturesToTrackDetector:
     def detect_rois(self, image: torch.Tensor, rois, stream=None, mask: torch.Tensor | None = None):
         """rois: iterable of (x, y, w, h).  Returns (corners (nroi, maxCorners, 2) f32,
         counts (nroi,) i32) device tensors; corners are in image coordinates.
+        counts are never negative: a ROI with more candidates (or a longer
+        accepted list) than the one-workgroup LDS selection holds, a whole frame
+        for instance, is selected by the wide path in global scratch, with the
+        same corners (context option "gftt_wide" = 1 sends every ROI there).
         mask: optional 2-D uint8 device tensor of the image's shape with
         stride(1) == 1 (any row stride: a slice of a larger tensor works); each
         ROI reads its own rectangle of it (tbdk_gftt_rois_masked).
@@ -710,12 +714,11 @@ class GoodFeaturesToTrackDetector:
         return corners, counts
 
     def detect(self, image: torch.Tensor, stream=None, mask: torch.Tensor | None = None) -> torch.Tensor:
-        """Whole image as one ROI -> (K, 2) corners (CornersDetector::detect, with its mask)."""
+        """Whole image as one ROI -> (K, 2) corners (CornersDetector::detect, with its mask).
+        Any frame size and any maxCorners: a frame with more candidates than the
+        LDS selection holds goes through the wide selection path (detect_rois)."""
         c, n = self.detect_rois(image, [(0, 0, image.shape[1], image.shape[0])], stream, mask)
-        k = int(n[0].item())
-        if k < 0:
-            raise _lib.TbdkError("candidate buffer overflow (image too large for one ROI)")
-        return c[0, :k]
+        return c[0, :int(n[0].item())]
 
 
 def subpix_params(win=(10, 10), zero_zone=(-1, -1), criteria=(3, 20, 0.03)) -> _lib.SubpixParams:

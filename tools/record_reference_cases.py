@@ -4,7 +4,8 @@ goodFeaturesToTrack, cornerMinEigenVal / cornerHarris, warpAffine,
 calcOpticalFlowFarneback, HOGDescriptor) on the cases of tests/_reference_cases.py
 (goodFeaturesToTrack under a mask: tests/_gftt_mask_cases.py; the corner maps and
 goodFeaturesToTrack on CV_32F images: tests/_gftt_f32_cases.py; cornerSubPix:
-tests/_subpix_cases.py)
+tests/_subpix_cases.py; goodFeaturesToTrack on whole frames:
+tests/_gftt_frame_cases.py)
 into tests/golden/reference_<op>.npz, through tools/reference_driver.cpp (how to
 build it: tools/record_reference_cases.md).
 
@@ -40,12 +41,13 @@ import _reference_cases as RC  # noqa: E402
 import _gftt_mask_cases as MC  # noqa: E402
 import _gftt_f32_cases as FC  # noqa: E402
 import _subpix_cases as SC  # noqa: E402
+import _gftt_frame_cases as WC  # noqa: E402
 
 LIMIT = 256 * 1024
 STATES = ("default", "noavx2")
 # the state each oracle file models where the two differ (README, numerics)
 MODELLED = {"pyramid": "both", "pyrlk": "both", "warpaffine": "both", "gftt": "noavx2", "gftt_mask": "noavx2",
-            "cornermaps": "noavx2", "gftt_f32": "noavx2", "subpix": "both",
+            "cornermaps": "noavx2", "gftt_f32": "noavx2", "subpix": "both", "gftt_frame": "noavx2",
             "farneback": "noavx2", "farneback_box": "noavx2", "hog": "default"}
 
 
@@ -217,6 +219,24 @@ def rec_gftt_f32(d):
     return cases, dict(nmaps=np.array(len(FC.map_cases()), np.int32))
 
 
+def rec_gftt_frame(d):
+    """goodFeaturesToTrack on whole frames (tests/_gftt_frame_cases.py): the lists whole, as int16 pairs"""
+    cases = []
+    for name, mk, maxc, ql, md, block, harris, _ in WC.CASES:
+        img = WC.frame(name)
+        h, w = img.shape
+        files = dict(a=img)
+        if mk != "none":
+            files["mask"] = WC.mask(mk, name)
+        kw = dict(depth="32f") if img.dtype == np.float32 else dict(cn=1)
+        _, rd = d.run("gftt", files, w=w, h=h, **kw, maxc=maxc, ql=ql, md=md, block=block, harris=harris,
+                      k=WC.HARRIS_K)
+        c = rd("c", np.float32).reshape(-1, 2)
+        assert np.array_equal(c, c.astype(np.int16))
+        cases.append((dict(c=c.astype(np.int16)), {}))
+    return cases, {}
+
+
 def rec_subpix(d):
     """cornerSubPix (tests/_subpix_cases.py): per image its point set (the 8-bit
     image's goodFeaturesToTrack corners, moved copies, special points), stored in
@@ -375,13 +395,13 @@ def merge(op, rec, whole_limit):
 
 
 RECORDERS = {"pyramid": rec_pyramid, "pyrlk": rec_pyrlk, "gftt": rec_gftt, "gftt_mask": rec_gftt_mask,
-             "cornermaps": rec_cornermaps, "gftt_f32": rec_gftt_f32, "subpix": rec_subpix,
+             "cornermaps": rec_cornermaps, "gftt_f32": rec_gftt_f32, "subpix": rec_subpix, "gftt_frame": rec_gftt_frame,
              "warpaffine": rec_warpaffine, "farneback": rec_farneback, "farneback_box": rec_farneback_box,
              "hog": rec_hog}
 # bytes up to which an output is stored whole (tests/_reference_cases.py: WHOLE_LIMIT).  The kernels are
 # compared with the box Farneback flows within a tolerance, so all six stay whole (about 7 KB under LIMIT)
 WHOLE = {"farneback": 20480, "farneback_box": 72800, "pyrlk": 1 << 20, "gftt": 1 << 20, "gftt_mask": 1 << 20,
-         "hog": 16384, "subpix": 1 << 20}
+         "hog": 16384, "subpix": 1 << 20, "gftt_frame": 1 << 20}
 # (gftt_f32: maps above RC.WHOLE_LIMIT as row CRCs; its corner lists are far below it)
 
 
@@ -414,6 +434,8 @@ def case_label(op, i):
         return f"{kind} roi {r} mask {mk} ({maxc}, {ql}, {md}) block {block}" + (" harris" if harris else "")
     if op == "subpix":
         return SC.label(i)
+    if op == "gftt_frame":
+        return WC.label(i)
     if op == "cornermaps":
         w, h, _ = RC.CMAP_SHAPES[i // len(RC.CMAP_MODES)]
         block, harris = RC.CMAP_MODES[i % len(RC.CMAP_MODES)]
