@@ -1204,6 +1204,117 @@ int tbdk_app_image_default_args(tbdk_app_image_args* args);
  * missing or malformed file is TBDK_EINVAL with nothing run. */
 int tbdk_app_run_images(const tbdk_app_image_args* args, tbdk_app_image_result* result);
 
+/* ---- KLT point tracker (the reference samples' lk_track loop) --------------
+ * samples/python/lk_track.py App.run (lines 48-86, minus the drawing) with
+ * samples/cpp/lkdemo.cpp's cornerSubPix (:84-85) and click-to-add: a long-lived,
+ * ordered set of point tracks that is tracked, pruned, masked and topped up
+ * frame after frame, entirely in device memory.  A step only enqueues work on
+ * the caller's stream: the host never reads the live count.
+ *
+ * Per step(frame):
+ *   1. the frame's pyramid is built;
+ *   2. with a previous frame, every track's last position is tracked prev -> cur
+ *      with tbdk_lk_sparse_fb's forward-backward check (both statuses gate and
+ *      max(|dx|, |dy|) < back_threshold in float32; lk_track.py:57-60 ignores
+ *      the statuses, the tracker does not).  Tracks that fail are removed, the
+ *      survivors keep their order, get the new position appended and drop their
+ *      oldest one beyond track_len;
+ *   3. if frame_idx % detect_interval == 0 or TBDK_KLT_DETECT_NOW: the mask is
+ *      255 with a filled circle of mask_radius zeroed at ((int)x, (int)y) of
+ *      every live track's last position (casts toward zero; the shape of
+ *      cv::circle(mask, c, r, 0, -1), clipped; mask_radius < 0: no mask);
+ *      goodFeaturesToTrack(frame, max_corners, quality_level, min_distance, mask,
+ *      block_size, use_harris, harris_k) on the whole frame; with subpix_win > 0
+ *      cornerSubPix((win, win), (-1, -1), COUNT|EPS 20, 0.03) on its corners;
+ *      every corner, in goodFeaturesToTrack's order, starts a track of length 1
+ *      with the next id (0, 1, 2, ... in creation order).  Beyond max_tracks the
+ *      strongest corners that fit are appended, the others counted as dropped;
+ *   4. frame_idx++, cur becomes prev.
+ * Frames are 8-bit, one channel. */
+typedef struct tbdk_klt_tracker tbdk_klt_tracker;
+
+typedef struct tbdk_klt_tracker_config {
+    int32_t width, height;
+    int32_t win, max_level, lk_iters;       /* PyrLK: window side, levels, criteria COUNT */
+    double  lk_epsilon;                     /* ... and EPS */
+    float   min_eig_threshold;
+    float   back_threshold;                 /* the check's distance bound, > 0 */
+    int32_t max_corners;                    /* goodFeaturesToTrack */
+    double  quality_level, min_distance;
+    int32_t block_size, use_harris;
+    double  harris_k;
+    int32_t detect_interval;                /* detection on frames 0, N, 2N, ... */
+    int32_t track_len;                      /* positions kept per track, 1..64 */
+    int32_t mask_radius;                    /* 0..64; < 0: detection without a mask */
+    int32_t subpix_win;                     /* cornerSubPix half window 1..15; 0: off */
+    int32_t max_tracks;                     /* capacity, 1..65536 */
+} tbdk_klt_tracker_config;
+
+/* statistics of the last step (plus the tbdk_klt_tracker_add_points calls since) */
+typedef struct tbdk_klt_tracker_stats {
+    int32_t tracks_in;   /* live tracks when the step began */
+    int32_t kept;        /* ... that passed the check (= tracks_in on the first frame) */
+    int32_t detected;    /* corners goodFeaturesToTrack returned (0 without detection) */
+    int32_t appended;    /* new tracks, detected or added */
+    int32_t dropped;     /* corners / added points beyond max_tracks */
+    int32_t next_id;     /* the id the next new track gets */
+    int32_t frame_idx;   /* index of the step's frame (-1 before the first step) */
+} tbdk_klt_tracker_stats;
+
+#define TBDK_KLT_DETECT_NOW 1
+
+/* lk_track.py's parameters: win 15, max_level 2, criteria (10, 0.03),
+ * min_eig_threshold 1e-4, back_threshold 1; goodFeaturesToTrack (500, 0.3, 7,
+ * blockSize 7); detect_interval 5, track_len 10, mask_radius 5; subpix_win 0;
+ * max_tracks 8192 */
+int tbdk_klt_tracker_default_config(int width, int height, tbdk_klt_tracker_config* cfg);
+/* Allocates everything a step needs (two pyramids, the two copies of the track
+ * state, the mask plane, the detector's output row and GFTT scratch of its own),
+ * so that steps allocate nothing.  TBDK_EINVAL: whatever tbdk_lk_sparse_fb,
+ * tbdk_gftt_rois_masked and tbdk_corner_sub_pix refuse for these parameters;
+ * track_len outside 1..64; detect_interval < 1; mask_radius > 64; subpix_win
+ * below 0; max_corners > max_tracks; max_tracks outside 1..65536. */
+int tbdk_klt_tracker_create(tbdk_ctx* ctx, const tbdk_klt_tracker_config* cfg, tbdk_klt_tracker** out);
+int tbdk_klt_tracker_destroy(tbdk_klt_tracker* tr);
+/* Empties the tracker: no tracks, ids from 0, frame_idx 0, no previous frame.
+ * Waits for the last step's stream. */
+int tbdk_klt_tracker_reset(tbdk_klt_tracker* tr);
+/* One frame (device, 8-bit one channel, pitch in bytes, read until the enqueued
+ * work is done).  flags: 0 or TBDK_KLT_DETECT_NOW.  TBDK_EINVAL (nothing
+ * enqueued, state unchanged): a null frame, pitch < width, unknown flags.
+ * Steps, add_points and reads of one tracker belong on one stream: a step on
+ * another stream than the previous one's without synchronising in between is
+ * the caller's error.  Timed as "pyr_build", "lk_sparse", "lk_sparse_back",
+ * "gftt", "gftt_wide", "corner_sub_pix" and the tracker's own "klt_compact",
+ * "klt_mask", "klt_append". */
+int tbdk_klt_tracker_step(tbdk_klt_tracker* tr, const uint8_t* frame, int pitch, int flags, void* stream);
+/* Appends n caller-supplied points (device, n x float2) as new tracks of length
+ * 1 under the capacity rule of detection (lkdemo's click-to-add; seeding from
+ * one's own detector).  The points are read when the stream gets there. */
+int tbdk_klt_tracker_add_points(tbdk_klt_tracker* tr, const float* device_pts, int n, void* stream);
+/* HOST outputs, any may be NULL: the live tracks in order, the first
+ * min(*n, cap) of them: ids, last_pts (float2), lens, hist (track_len float2
+ * per track, oldest first, zero beyond the track's length); *n: the live count;
+ * *stats: see above.  Synchronises the stream of the last step. */
+int tbdk_klt_tracker_read(tbdk_klt_tracker* tr, int32_t* ids, float* last_pts, int32_t* lens, float* hist, int cap,
+                          int* n, tbdk_klt_tracker_stats* stats);
+/* The device pointers of the state, for consumers that stay on the GPU (any may
+ * be NULL): count (one int32), ids, last_pts, lens and hist as in
+ * tbdk_klt_tracker_read, max_tracks entries each.  Valid until the next step;
+ * read them on the step's stream or after synchronising it. */
+int tbdk_klt_tracker_device_state(tbdk_klt_tracker* tr, const int32_t** count, const int32_t** ids,
+                                  const float** last_pts, const int32_t** lens, const float** hist);
+/* The tracker's detection mask on its own: writes `value` into the filled circle
+ * of `radius` (0..64) around ((int)x, (int)y) of each of the first
+ * min(*count_dev, n) points (count_dev NULL: n) and leaves the rest of the mask
+ * alone.  mask: device u8, width x height, pitch in bytes; pts: device, n x
+ * float2; count_dev: device int32 or NULL.  The circle is the one
+ * cv::circle(mask, c, radius, value, -1) draws (imgproc/src/drawing.cpp:1486-1628),
+ * clipped to the mask; centres may lie anywhere, a point that is not finite or
+ * beyond +-1e9 draws nothing.  Timed as "klt_mask". */
+int tbdk_mask_circles_u8(tbdk_ctx* ctx, uint8_t* mask, int width, int height, int pitch, const float* pts,
+                         const int32_t* count_dev, int n, int radius, int value, void* stream);
+
 /* ---- synthetic sequences (bench / test input) ----------------------------- */
 
 /* Renders frames [t0, t0+nframes) of the deterministic synthetic sequence of

@@ -782,6 +782,70 @@ private:
     tbdk_tbd* h_ = nullptr;
 };
 
+// The loop of the reference's KLT samples (samples/python/lk_track.py App.run:48-86,
+// samples/cpp/lkdemo.cpp's cornerSubPix and click-to-add) as one device-resident
+// object (tbdk_klt_tracker): step() tracks every live point with the
+// forward-backward check, drops the lost ones (both statuses gate, unlike
+// lk_track.py:57-60) and, every detect_interval frames, detects new corners away
+// from the live ones.  A step only enqueues work; read() synchronises.
+class KltTracker {
+public:
+    // the live tracks in order: hist holds trackLen float2 per track, oldest first, zero beyond lens[i]
+    struct State {
+        std::vector<int32_t> ids, lens;
+        std::vector<float> lastPts, hist;
+        tbdk_klt_tracker_stats stats;
+        int trackLen = 0;
+        size_t size() const { return ids.size(); }
+    };
+    KltTracker(Context& ctx, const tbdk_klt_tracker_config& cfg) : track_len_(cfg.track_len)
+    {
+        check(tbdk_klt_tracker_create(ctx.get(), &cfg, &h_), "tbdk_klt_tracker_create");
+    }
+    ~KltTracker() { tbdk_klt_tracker_destroy(h_); }
+    KltTracker(const KltTracker&) = delete;
+    KltTracker& operator=(const KltTracker&) = delete;
+    static tbdk_klt_tracker_config defaultConfig(int width, int height)
+    {
+        tbdk_klt_tracker_config c;
+        check(tbdk_klt_tracker_default_config(width, height, &c), "tbdk_klt_tracker_default_config");
+        return c;
+    }
+    void step(const GpuImage& frame, bool detectNow = false, void* stream = nullptr)
+    {
+        check(tbdk_klt_tracker_step(h_, frame.data, frame.pitch, detectNow ? TBDK_KLT_DETECT_NOW : 0, stream),
+              "tbdk_klt_tracker_step");
+    }
+    // n device points (float2) become new tracks (lkdemo's click-to-add)
+    void addPoints(const float* devicePts, int n, void* stream = nullptr)
+    {
+        check(tbdk_klt_tracker_add_points(h_, devicePts, n, stream), "tbdk_klt_tracker_add_points");
+    }
+    void reset() { check(tbdk_klt_tracker_reset(h_), "tbdk_klt_tracker_reset"); }
+    State read()
+    {
+        State s;
+        int n = 0;
+        check(tbdk_klt_tracker_read(h_, nullptr, nullptr, nullptr, nullptr, 0, &n, &s.stats), "tbdk_klt_tracker_read");
+        const size_t k = n > 0 ? (size_t)n : 0;
+        s.trackLen = track_len_;
+        s.ids.resize(k);
+        s.lens.resize(k);
+        s.lastPts.resize(2 * k);
+        s.hist.resize(2 * k * (size_t)track_len_);
+        if (k)
+            check(tbdk_klt_tracker_read(h_, s.ids.data(), s.lastPts.data(), s.lens.data(), s.hist.data(), (int)k, &n,
+                                        &s.stats),
+                  "tbdk_klt_tracker_read");
+        return s;
+    }
+    tbdk_klt_tracker* get() const { return h_; }
+
+private:
+    tbdk_klt_tracker* h_ = nullptr;
+    int track_len_ = 0;
+};
+
 // The sample's whole per-frame path (samples/gpu/tbd.cpp:568-622) on a TbdLoop:
 // colour frame -> cvtColor -> optional resize -> HOG detectMultiScale -> the
 // loop (tbdk_tbd_step_image).  `loop` and `ctx` must outlive it.

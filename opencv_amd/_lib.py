@@ -138,6 +138,23 @@ class SubpixParams(C.Structure):
                 ("criteria", C.c_int32), ("max_count", C.c_int32), ("epsilon", C.c_double)]
 
 
+class KltTrackerConfig(C.Structure):
+    _fields_ = [("width", C.c_int32), ("height", C.c_int32), ("win", C.c_int32), ("max_level", C.c_int32),
+                ("lk_iters", C.c_int32), ("lk_epsilon", C.c_double), ("min_eig_threshold", C.c_float),
+                ("back_threshold", C.c_float), ("max_corners", C.c_int32), ("quality_level", C.c_double),
+                ("min_distance", C.c_double), ("block_size", C.c_int32), ("use_harris", C.c_int32),
+                ("harris_k", C.c_double), ("detect_interval", C.c_int32), ("track_len", C.c_int32),
+                ("mask_radius", C.c_int32), ("subpix_win", C.c_int32), ("max_tracks", C.c_int32)]
+
+
+class KltTrackerStats(C.Structure):
+    _fields_ = [("tracks_in", C.c_int32), ("kept", C.c_int32), ("detected", C.c_int32), ("appended", C.c_int32),
+                ("dropped", C.c_int32), ("next_id", C.c_int32), ("frame_idx", C.c_int32)]
+
+
+TBDK_KLT_DETECT_NOW = 1
+
+
 class TrackerArgs(C.Structure):
     _fields_ = [("cost_of_non_assignment", C.c_double), ("time_window_size", C.c_int32),
                 ("track_age_threshold", C.c_int32), ("track_visibility_threshold", C.c_double),
@@ -268,6 +285,17 @@ SIGNATURES = {
     "tbdk_corner_sub_pix": (C.c_int, [C.c_void_p, C.c_void_p, C.c_int, C.c_int, C.c_int, C.c_int, C.c_void_p,
                                       C.c_void_p, C.c_int, C.c_int, C.POINTER(SubpixParams), C.c_void_p]),
     "tbdk_corner_sub_pix_mask": (C.c_int, [C.POINTER(SubpixParams), C.c_void_p]),
+    "tbdk_klt_tracker_default_config": (C.c_int, [C.c_int, C.c_int, C.POINTER(KltTrackerConfig)]),
+    "tbdk_klt_tracker_create": (C.c_int, [C.c_void_p, C.POINTER(KltTrackerConfig), C.POINTER(C.c_void_p)]),
+    "tbdk_klt_tracker_destroy": (C.c_int, [C.c_void_p]),
+    "tbdk_klt_tracker_reset": (C.c_int, [C.c_void_p]),
+    "tbdk_klt_tracker_step": (C.c_int, [C.c_void_p, C.c_void_p, C.c_int, C.c_int, C.c_void_p]),
+    "tbdk_klt_tracker_add_points": (C.c_int, [C.c_void_p, C.c_void_p, C.c_int, C.c_void_p]),
+    "tbdk_klt_tracker_read": (C.c_int, [C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_int,
+                                        C.POINTER(C.c_int), C.POINTER(KltTrackerStats)]),
+    "tbdk_klt_tracker_device_state": (C.c_int, [C.c_void_p] + [C.POINTER(C.c_void_p)] * 5),
+    "tbdk_mask_circles_u8": (C.c_int, [C.c_void_p, C.c_void_p, C.c_int, C.c_int, C.c_int, C.c_void_p, C.c_void_p,
+                                       C.c_int, C.c_int, C.c_int, C.c_void_p]),
     "tbdk_box_propagate": (C.c_int, [C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_int,
                                      C.c_int, C.c_void_p, C.c_void_p]),
     "tbdk_ransac_default_params": (C.c_int, [C.POINTER(RansacParams)]),

@@ -794,3 +794,166 @@ def synth_render(seed: int, width: int, height: int, nobj: int, t0: int, nframes
                                          C.c_void_p(frames.data_ptr()), width, C.c_void_p(gt.data_ptr()),
                                          _stream_ptr(stream)), "tbdk_synth_render")
     return frames, gt[:, :nobj]
+
+
+def mask_circles(mask: torch.Tensor, pts: torch.Tensor, radius: int, value: int = 0,
+                 count: torch.Tensor | None = None, ctx: Context | None = None, stream=None) -> torch.Tensor:
+    """cv::circle(mask, (int(x), int(y)), radius, value, -1) for every point, in
+    place and clipped to the mask (tbdk_mask_circles_u8; imgproc/src/drawing.cpp:1486-1628):
+    the disc lk_track.py:77-78 cuts out of its detection mask.  mask: 2-D uint8
+    device tensor with stride(1) == 1 (any row stride); pts: float32 (n, 2) device
+    tensor; radius 0..64; count: optional int32 device tensor (1,), only the first
+    min(count, n) points are drawn.  Centres may lie anywhere; a point that is not
+    finite draws nothing.  Returns mask."""
+    if not isinstance(mask, torch.Tensor) or mask.dtype != torch.uint8 or mask.dim() != 2 or not mask.is_cuda or \
+            mask.stride(1) != 1:
+        raise _lib.TbdkError("mask_circles: mask must be a 2-D uint8 device tensor with stride(1) == 1")
+    if not isinstance(pts, torch.Tensor) or pts.dtype != torch.float32 or pts.device != mask.device or \
+            pts.dim() != 2 or pts.shape[1] != 2 or not pts.is_contiguous():
+        raise _lib.TbdkError("mask_circles: pts must be a contiguous float32 (n, 2) tensor on the mask's device")
+    if count is not None and (not isinstance(count, torch.Tensor) or count.dtype != torch.int32 or
+                              count.device != mask.device or count.numel() != 1):
+        raise _lib.TbdkError("mask_circles: count must be an int32 tensor of one element on the mask's device")
+    ctx = ctx or Context.get(mask.device.index or 0)
+    _lib.check(ctx.lib.tbdk_mask_circles_u8(
+        ctx.handle, C.c_void_p(mask.data_ptr()), mask.shape[1], mask.shape[0], int(mask.stride(0)),
+        C.c_void_p(pts.data_ptr()), C.c_void_p(count.data_ptr()) if count is not None else None, int(pts.shape[0]),
+        int(radius), int(value), _stream_ptr(stream)), "tbdk_mask_circles_u8")
+    return mask
+
+
+@dataclass
+class KltTrackerState:
+    """KltTracker.read(): the live tracks in order"""
+    ids: np.ndarray       # (n,) int32
+    last_pts: np.ndarray  # (n, 2) float32
+    lens: np.ndarray      # (n,) int32
+    hist: np.ndarray      # (n, track_len, 2) float32, oldest first, zero beyond lens
+    stats: dict           # tbdk_klt_tracker_stats of the last step
+
+
+class KltTracker:
+    """The loop of the reference's KLT samples (samples/python/lk_track.py App.run,
+    samples/cpp/lkdemo.cpp) as one device-resident object (tbdk_klt_tracker, see
+    include/tbdk.h): step(frame) tracks every live point with the forward-backward
+    check, drops the lost ones, and every detect_interval frames detects new
+    corners away from the live ones; nothing is read back until read().
+
+    KltTracker(cfg=None, ctx=None, **overrides): cfg a _lib.KltTrackerConfig
+    (KltTracker.default_config(width, height): lk_track's parameters; without one,
+    width= and height= are required), overrides its fields by name (win, max_level, lk_iters, lk_epsilon, min_eig_threshold, back_threshold,
+    max_corners, quality_level, min_distance, block_size, use_harris, harris_k,
+    detect_interval, track_len, mask_radius, subpix_win, max_tracks).
+
+    Unlike lk_track.py:57-60, which looks only at the distance, a point is kept
+    only if both PyrLK passes also report it found (tbdk_lk_sparse_fb)."""
+
+    def __init__(self, cfg: _lib.KltTrackerConfig | None = None, ctx: Context | None = None, device: int = 0,
+                 **overrides):
+        self.handle = None
+        self.ctx = ctx or Context.get(device)
+        if cfg is None:
+            if "width" not in overrides or "height" not in overrides:
+                raise _lib.TbdkError("KltTracker: a configuration, or width= and height=")
+            cfg = self.default_config(overrides["width"], overrides["height"])
+        self.cfg = cfg
+        names = {f[0] for f in _lib.KltTrackerConfig._fields_}
+        for k, v in overrides.items():
+            if k not in names:
+                raise _lib.TbdkError(f"KltTracker: unknown configuration field {k}")
+            setattr(self.cfg, k, v)
+        h = C.c_void_p()
+        _lib.check(self.ctx.lib.tbdk_klt_tracker_create(self.ctx.handle, C.byref(self.cfg), C.byref(h)),
+                   "tbdk_klt_tracker_create")
+        self.handle = h
+        self._keep = None
+
+    @staticmethod
+    def default_config(width: int, height: int) -> _lib.KltTrackerConfig:
+        cfg = _lib.KltTrackerConfig()
+        _lib.check(_lib.load().tbdk_klt_tracker_default_config(int(width), int(height), C.byref(cfg)),
+                   "tbdk_klt_tracker_default_config")
+        return cfg
+
+    def __del__(self):
+        h = getattr(self, "handle", None)
+        if h is not None and h.value:
+            try:
+                self.ctx.lib.tbdk_klt_tracker_destroy(h)
+            except Exception:
+                pass
+            self.handle = None
+
+    def step(self, frame: torch.Tensor, detect_now: bool = False, stream=None) -> None:
+        """One frame: a 2-D uint8 device tensor of the tracker's size with
+        stride(1) == 1.  Only enqueues work; the tracker keeps a reference to the
+        frame until the next step.  Steps, add_points and read belong on one stream."""
+        if not isinstance(frame, torch.Tensor) or frame.dtype != torch.uint8 or frame.dim() != 2 or \
+                not frame.is_cuda or frame.stride(1) != 1 or \
+                tuple(frame.shape) != (self.cfg.height, self.cfg.width):
+            raise _lib.TbdkError("KltTracker.step expects a 2-D uint8 device tensor of the tracker's size")
+        _lib.check(self.ctx.lib.tbdk_klt_tracker_step(self.handle, C.c_void_p(frame.data_ptr()), int(frame.stride(0)),
+                                                      _lib.TBDK_KLT_DETECT_NOW if detect_now else 0,
+                                                      _stream_ptr(stream)), "tbdk_klt_tracker_step")
+        self._keep = frame
+
+    def add_points(self, pts, stream=None) -> None:
+        """New tracks at caller-supplied points ((n, 2) float32, a device tensor or
+        anything numpy converts), under the capacity rule of detection."""
+        if not isinstance(pts, torch.Tensor):
+            pts = torch.from_numpy(np.ascontiguousarray(pts, np.float32).reshape(-1, 2)).cuda(self.ctx.device)
+        if pts.dtype != torch.float32 or not pts.is_cuda or pts.dim() != 2 or pts.shape[1] != 2:
+            raise _lib.TbdkError("KltTracker.add_points expects float32 (n, 2) points")
+        pts = pts.contiguous()
+        _lib.check(self.ctx.lib.tbdk_klt_tracker_add_points(self.handle, C.c_void_p(pts.data_ptr()), int(pts.shape[0]),
+                                                            _stream_ptr(stream)), "tbdk_klt_tracker_add_points")
+        self._keep_pts = pts
+
+    def reset(self) -> None:
+        _lib.check(self.ctx.lib.tbdk_klt_tracker_reset(self.handle), "tbdk_klt_tracker_reset")
+
+    def read(self) -> KltTrackerState:
+        """Host copies of the live tracks and the last step's statistics
+        (synchronises the stream of the last step)."""
+        n, st = C.c_int(), _lib.KltTrackerStats()
+        _lib.check(self.ctx.lib.tbdk_klt_tracker_read(self.handle, None, None, None, None, 0, C.byref(n), C.byref(st)),
+                   "tbdk_klt_tracker_read")
+        k, L = max(int(n.value), 0), int(self.cfg.track_len)
+        ids, lens = np.zeros(k, np.int32), np.zeros(k, np.int32)
+        last, hist = np.zeros((k, 2), np.float32), np.zeros((k, L, 2), np.float32)
+        if k:
+            _lib.check(self.ctx.lib.tbdk_klt_tracker_read(
+                self.handle, ids.ctypes.data_as(C.c_void_p), last.ctypes.data_as(C.c_void_p),
+                lens.ctypes.data_as(C.c_void_p), hist.ctypes.data_as(C.c_void_p), k, C.byref(n), C.byref(st)),
+                "tbdk_klt_tracker_read")
+        return KltTrackerState(ids, last, lens, hist, {f[0]: int(getattr(st, f[0])) for f in st._fields_})
+
+    def tracks(self) -> dict:
+        """{id: (len, 2) float32 positions, oldest first} (lk_track's self.tracks)"""
+        s = self.read()
+        return {int(i): s.hist[k, :int(s.lens[k])].copy() for k, i in enumerate(s.ids)}
+
+    def device_state(self):
+        """(count (1,) int32, ids, last_pts (max_tracks, 2), lens, hist (max_tracks,
+        track_len, 2)) as torch views of the tracker's device memory, valid until
+        the next step; entries at and beyond count are unspecified."""
+        p = [C.c_void_p() for _ in range(5)]
+        _lib.check(self.ctx.lib.tbdk_klt_tracker_device_state(self.handle, *[C.byref(x) for x in p]),
+                   "tbdk_klt_tracker_device_state")
+        M, L = int(self.cfg.max_tracks), int(self.cfg.track_len)
+        shapes = [((1,), torch.int32), ((M,), torch.int32), ((M, 2), torch.float32), ((M,), torch.int32),
+                  ((M, L, 2), torch.float32)]
+        return tuple(_device_view(x.value, sh, dt, self.ctx.device) for x, (sh, dt) in zip(p, shapes))
+
+
+class _DevMem:
+    """__cuda_array_interface__ over library-owned device memory"""
+
+    def __init__(self, ptr: int, shape, typestr: str):
+        self.__cuda_array_interface__ = {"shape": tuple(shape), "typestr": typestr, "data": (int(ptr), False),
+                                         "version": 2}
+
+
+def _device_view(ptr: int, shape, dtype: torch.dtype, device: int) -> torch.Tensor:
+    typestr = {torch.int32: "<i4", torch.float32: "<f4", torch.uint8: "|u1"}[dtype]
+    return torch.as_tensor(_DevMem(ptr, shape, typestr), device=f"cuda:{device}")

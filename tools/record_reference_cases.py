@@ -42,13 +42,14 @@ import _gftt_mask_cases as MC  # noqa: E402
 import _gftt_f32_cases as FC  # noqa: E402
 import _subpix_cases as SC  # noqa: E402
 import _gftt_frame_cases as WC  # noqa: E402
+import _klt_tracker_oracle as KT  # noqa: E402
 
 LIMIT = 256 * 1024
 STATES = ("default", "noavx2")
 # the state each oracle file models where the two differ (README, numerics)
 MODELLED = {"pyramid": "both", "pyrlk": "both", "warpaffine": "both", "gftt": "noavx2", "gftt_mask": "noavx2",
             "cornermaps": "noavx2", "gftt_f32": "noavx2", "subpix": "both", "gftt_frame": "noavx2",
-            "farneback": "noavx2", "farneback_box": "noavx2", "hog": "default"}
+            "circle": "both", "farneback": "noavx2", "farneback_box": "noavx2", "hog": "default"}
 
 
 class Driver:
@@ -264,6 +265,19 @@ def rec_subpix(d):
     return cases, extra
 
 
+def rec_circle(d):
+    """circle(img, c, r, Scalar(0), -1) on a 255-filled image (tests/_klt_tracker_oracle.py: CIRCLE_CASES): the
+    drawn pixels, bit-packed"""
+    w, h = KT.CIRCLE_SIZE
+    cases = []
+    for cx, cy, r in KT.CIRCLE_CASES:
+        _, rd = d.run("circle", {}, w=w, h=h, cx=cx, cy=cy, r=r)
+        m = rd("m", np.uint8).reshape(h, w)
+        assert np.isin(m, (0, 255)).all()
+        cases.append((dict(m=np.packbits(m == 0)), {}))
+    return cases, {}
+
+
 def warp_table():
     """(flags, border, bval, sw, sh, dw, dh, M) per case: 4 interpolations x 6 borders x
     the inverse flag on matrices drawn from a fixed seed, then the degenerate matrices"""
@@ -396,7 +410,7 @@ def merge(op, rec, whole_limit):
 
 RECORDERS = {"pyramid": rec_pyramid, "pyrlk": rec_pyrlk, "gftt": rec_gftt, "gftt_mask": rec_gftt_mask,
              "cornermaps": rec_cornermaps, "gftt_f32": rec_gftt_f32, "subpix": rec_subpix, "gftt_frame": rec_gftt_frame,
-             "warpaffine": rec_warpaffine, "farneback": rec_farneback, "farneback_box": rec_farneback_box,
+             "circle": rec_circle, "warpaffine": rec_warpaffine, "farneback": rec_farneback, "farneback_box": rec_farneback_box,
              "hog": rec_hog}
 # bytes up to which an output is stored whole (tests/_reference_cases.py: WHOLE_LIMIT).  The kernels are
 # compared with the box Farneback flows within a tolerance, so all six stay whole (about 7 KB under LIMIT)
@@ -436,6 +450,8 @@ def case_label(op, i):
         return SC.label(i)
     if op == "gftt_frame":
         return WC.label(i)
+    if op == "circle":
+        return "centre ({}, {}) radius {}".format(*KT.CIRCLE_CASES[i])
     if op == "cornermaps":
         w, h, _ = RC.CMAP_SHAPES[i // len(RC.CMAP_MODES)]
         block, harris = RC.CMAP_MODES[i % len(RC.CMAP_MODES)]

@@ -22,6 +22,8 @@
 //   fb    a= b= w= h= ps= lv= ws= it= pn= sg= flags= [init=]               -> f (f32 pairs)
 //   hoggrad a= w= h= cn= gamma= signed=            -> g (f32 pairs), qa (u8 pairs)
 //   hogdet  a= w= h= cn= win=64|48 hit= group=     -> loc (i32 pairs), wt (f64), r (i32 x4), rw (f64), svm (f32)
+//   circle  w= h= cx= cy= r=                       -> m (u8): circle(img, (cx, cy), r, Scalar(0), -1) on a 255-filled
+//                                                  CV_8UC1 image (no input image)
 #include <cmath>
 #include <cstdio>
 #include <cstdlib>
@@ -90,6 +92,12 @@ static Mat image_depth(const std::string& key, int w, int h)
 static int run(const std::string& op, const std::string& out)
 {
     const int w = iarg("w"), h = iarg("h"), cn = has("cn") ? iarg("cn") : 1;
+    if (op == "circle") {
+        Mat m(h, w, CV_8UC1, Scalar(255));
+        circle(m, Point(iarg("cx"), iarg("cy")), iarg("r"), Scalar(0), -1);
+        wr(out, "m", m);
+        return 0;
+    }
     Mat a = op == "gftt" || op == "cmap" || op == "subpix" ? image_depth("a", w, h) : image("a", w, h, cn);
     if (op == "pyr") {
         std::vector<Mat> pyr;
