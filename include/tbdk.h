@@ -707,6 +707,68 @@ int tbdk_warp_affine_u8(tbdk_ctx* ctx, const uint8_t* src, int src_width, int sr
                         uint8_t* dst, int dst_width, int dst_height, int dst_pitch, const double* M,
                         int flags, int border, int border_value, void* stream);
 
+/* ---- remap, warpPerspective, warp by a dense flow --------------------------- */
+
+/* map kinds of tbdk_remap (cv::remap's map1 / map2 types) */
+#define TBDK_MAP_32FC2 0             /* map1: CV_32FC2 (x, y); map2 unused */
+#define TBDK_MAP_32FC1 1             /* map1: CV_32FC1 x, map2: CV_32FC1 y */
+#define TBDK_MAP_16SC2 2             /* map1: CV_16SC2 (x, y); map2: CV_16UC1 fraction words (convertMaps' form),
+                                      * or NULL: whole-pixel positions, TBDK_INTER_NEAREST only */
+
+/* Replaces cv::cuda::remap(src, dst, xmap, ymap, interpolation, borderMode, borderValue, stream)
+ * (modules/cudawarping/include/opencv2/cudawarping.hpp) with the numerics of the CPU cv::remap
+ * (imgproc/src/imgwarp.cpp:1664-1830: 5-bit sub-pixel positions, 15-bit fixed-point weights for 8U,
+ * the float weight table for 32F): bit-exact with it, whatever the map holds.  NaN, +-inf and values
+ * far outside the image are valid map entries (cvRound gives 0x80000000 for them, which saturates
+ * to -32768); no map value makes the kernel read outside the source.
+ *   src, dst : device images of `cn` (1..4) channels, pix TBDK_PIX_U8 or TBDK_PIX_F32, pitches in
+ *              bytes (F32: pointers and pitches multiples of 4); every side below 32767, as the
+ *              reference asserts; dst must not alias src or a map; an empty dst is a no-op
+ *   map1/2   : device maps of dst's size (map_kind above; float maps 4-byte, short maps 2-byte
+ *              aligned).  A fraction word is taken & 1023, as the reference does.  With
+ *              TBDK_INTER_NEAREST a fraction plane moves the position by the reference's
+ *              NNDeltaTab_i (plus one where the fraction is below one half, imgwarp.cpp:237-238).
+ *              TBDK_MAP_16SC2 without map2 and an interpolating mode is TBDK_EINVAL (the reference
+ *              reads the shorts as floats there)
+ *   interpolation : TBDK_INTER_NEAREST / LINEAR / AREA (= LINEAR), and CUBIC for TBDK_PIX_U8
+ *              (TBDK_PIX_F32 with CUBIC is TBDK_EINVAL)
+ *   border   : TBDK_BORDER_*; border_value[4], each saturated to the pixel type per channel
+ * Asynchronous on `stream`; no host synchronisation, no allocation.  Timing name "remap". */
+int tbdk_remap(tbdk_ctx* ctx, const void* src, int pix, int cn, int src_width, int src_height, int src_pitch,
+               void* dst, int dst_width, int dst_height, int dst_pitch, const void* map1, int map1_pitch,
+               const void* map2, int map2_pitch, int map_kind, int interpolation, int border,
+               const double* border_value, void* stream);
+
+/* tbdk_remap by the map grid + sign * flow, formed in registers and never stored:
+ * mapx = (float)x + sign * flow.x, mapy = (float)y + sign * flow.y (one float32 addition each),
+ * decoded as a CV_32FC2 map.  Equal, byte for byte, to tbdk_remap with that map.
+ *   flow : device CV_32FC2 (dx, dy) per destination pixel, as tbdk_farneback and tbdk_lk_dense
+ *          write it; flow_pitch in bytes
+ *   sign : +1 samples at p + flow (warps frame B onto frame A, given the flow A -> B);
+ *          -1 samples at p - flow (warp_flow of samples/python/opt_flow.py)
+ * Timing name "remap_flow". */
+int tbdk_remap_flow(tbdk_ctx* ctx, const void* src, int pix, int cn, int src_width, int src_height, int src_pitch,
+                    void* dst, int dst_width, int dst_height, int dst_pitch, const float* flow, int flow_pitch,
+                    int sign, int interpolation, int border, const double* border_value, void* stream);
+
+/* Replaces cv::cuda::warpPerspective(src, dst, M, dsize, flags, borderMode, borderValue, stream)
+ * with the numerics of the CPU cv::warpPerspective (imgwarp.cpp:2706-2797, 2881-2990): the
+ * projective map in double, formed from each 64-column block's origin as the reference forms it
+ * (wider blocks for destinations of fewer than 16 rows), then tbdk_remap's sampling.
+ *   M     : HOST 3x3 row-major double matrix, src -> dst unless TBDK_WARP_INVERSE_MAP; inverted on
+ *           the host as cv::invert does (a singular matrix gives the zero matrix: every pixel then
+ *           samples (0, 0)).  All nine entries must be finite, otherwise TBDK_EINVAL
+ *   flags : TBDK_INTER_* | TBDK_WARP_INVERSE_MAP
+ * Not equal to tbdk_warp_affine_u8 for an affine M: the two round differently, as the
+ * reference's two functions do.  Timing name "warp_perspective". */
+int tbdk_warp_perspective(tbdk_ctx* ctx, const void* src, int pix, int cn, int src_width, int src_height,
+                          int src_pitch, void* dst, int dst_width, int dst_height, int dst_pitch, const double* M,
+                          int flags, int border, const double* border_value, void* stream);
+
+/* The host-side inverse tbdk_warp_perspective takes (cv::invert's 3x3 CV_64F branch), exported
+ * for the tests; host only, needs no GPU */
+int tbdk_warp_perspective_invert(const double* M, double* out);
+
 /* ---- image front end: cvtColor, resize ------------------------------------- */
 
 /* colour conversion codes: the reference's values (imgproc.hpp ColorConversionCodes) */

@@ -622,6 +622,78 @@ private:
 
 }  // namespace cuda
 
+// cv::Scalar for a border value: four doubles, each saturated to the pixel type per channel
+struct Scalar {
+    double val[4] = {0, 0, 0, 0};
+    Scalar() = default;
+    Scalar(double v0, double v1 = 0, double v2 = 0, double v3 = 0) : val{v0, v1, v2, v3} {}
+};
+
+namespace detail {
+inline int warp_pix(const GpuMatView& src, const GpuMatView& dst, const char* what)
+{
+    if (src.depth != dst.depth || src.cn != dst.cn || (src.depth != DEPTH_8U && src.depth != DEPTH_32F))
+        throw Error(TBDK_EINVAL, what);
+    return src.depth == DEPTH_8U ? TBDK_PIX_U8 : TBDK_PIX_F32;
+}
+}  // namespace detail
+
+// cv::cuda::remap(src, dst, xmap, ymap, interpolation, borderMode, borderValue, stream)
+// (cudawarping.hpp) with the CPU cv::remap's bits, for CV_8UC1..4 and CV_32FC1..4.
+// The maps are views of dst's size: two CV_32FC1 planes as cv::cuda::remap takes
+// them, or cv::remap's other forms: one CV_32FC2 view (ymap empty), or a CV_16SC2
+// view (depth DEPTH_16S, cn 2) with an optional CV_16UC1 fraction plane.
+constexpr int DEPTH_16S = 3;
+inline void remap(Context& ctx, const GpuMatView& src, GpuMatView& dst, const GpuMatView& xmap, const GpuMatView& ymap,
+                  int interpolation, int borderMode = TBDK_BORDER_CONSTANT, const Scalar& borderValue = Scalar(),
+                  void* stream = nullptr)
+{
+    const int pix = detail::warp_pix(src, dst, "remap");
+    int kind;
+    if (xmap.depth == DEPTH_32F && xmap.cn == 2) kind = TBDK_MAP_32FC2;
+    else if (xmap.depth == DEPTH_32F && xmap.cn == 1 && ymap.data && ymap.depth == DEPTH_32F && ymap.cn == 1)
+        kind = TBDK_MAP_32FC1;
+    else if (xmap.depth == DEPTH_16S && xmap.cn == 2 && (!ymap.data || (ymap.depth == DEPTH_16U && ymap.cn == 1)))
+        kind = TBDK_MAP_16SC2;
+    else throw Error(TBDK_EINVAL, "remap: map types");
+    if (xmap.width != dst.width || xmap.height != dst.height ||
+        (kind != TBDK_MAP_32FC2 && ymap.data && (ymap.width != dst.width || ymap.height != dst.height)))
+        throw Error(TBDK_EINVAL, "remap: map size");
+    check(tbdk_remap(ctx.get(), src.data, pix, src.cn, src.width, src.height, src.pitch, dst.data, dst.width,
+                     dst.height, dst.pitch, xmap.data, xmap.pitch, kind == TBDK_MAP_32FC2 ? nullptr : ymap.data,
+                     ymap.pitch, kind, interpolation, borderMode, borderValue.val, stream),
+          "tbdk_remap");
+}
+
+// remap by grid + sign * flow without storing the map: flow is the CV_32FC2 plane
+// FarnebackOpticalFlow / DensePyrLKOpticalFlow write (dst's size).  sign +1 warps
+// frame B onto frame A given the flow A -> B; -1 is opt_flow.py's warp_flow.
+inline void remapFlow(Context& ctx, const GpuMatView& src, GpuMatView& dst, const GpuMatView& flow, int sign = 1,
+                      int interpolation = TBDK_INTER_LINEAR, int borderMode = TBDK_BORDER_CONSTANT,
+                      const Scalar& borderValue = Scalar(), void* stream = nullptr)
+{
+    const int pix = detail::warp_pix(src, dst, "remapFlow");
+    if (flow.depth != DEPTH_32F || flow.cn != 2 || flow.width != dst.width || flow.height != dst.height)
+        throw Error(TBDK_EINVAL, "remapFlow: flow must be CV_32FC2 of dst's size");
+    check(tbdk_remap_flow(ctx.get(), src.data, pix, src.cn, src.width, src.height, src.pitch, dst.data, dst.width,
+                          dst.height, dst.pitch, static_cast<const float*>(flow.data), flow.pitch, sign,
+                          interpolation, borderMode, borderValue.val, stream),
+          "tbdk_remap_flow");
+}
+
+// cv::cuda::warpPerspective(src, dst, M, dsize, flags, borderMode, borderValue, stream)
+// (cudawarping.hpp) with the CPU cv::warpPerspective's bits; dsize is dst's size;
+// M is a host 3x3 row-major matrix.
+inline void warpPerspective(Context& ctx, const GpuMatView& src, GpuMatView& dst, const double M[9],
+                            int flags = TBDK_INTER_LINEAR, int borderMode = TBDK_BORDER_CONSTANT,
+                            const Scalar& borderValue = Scalar(), void* stream = nullptr)
+{
+    const int pix = detail::warp_pix(src, dst, "warpPerspective");
+    check(tbdk_warp_perspective(ctx.get(), src.data, pix, src.cn, src.width, src.height, src.pitch, dst.data,
+                                dst.width, dst.height, dst.pitch, M, flags, borderMode, borderValue.val, stream),
+          "tbdk_warp_perspective");
+}
+
 // cv::cornerSubPix(image, corners, winSize, zeroZone, criteria) (imgproc.hpp;
 // imgproc/src/cornersubpix.cpp:44-156; the reference has no CUDA form) on the
 // device, with the CPU function's bits: corners is device memory, nrows x rowCap

@@ -304,6 +304,17 @@ SIGNATURES = {
                                             C.c_void_p, C.c_void_p]),
     "tbdk_warp_affine_u8": (C.c_int, [C.c_void_p, C.c_void_p, C.c_int, C.c_int, C.c_int, C.c_void_p, C.c_int, C.c_int,
                                       C.c_int, C.POINTER(C.c_double), C.c_int, C.c_int, C.c_int, C.c_void_p]),
+    # ctx, src, pix, cn, sw, sh, spitch, dst, dw, dh, dpitch, ...
+    "tbdk_remap": (C.c_int, [C.c_void_p, C.c_void_p, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, C.c_void_p, C.c_int,
+                             C.c_int, C.c_int, C.c_void_p, C.c_int, C.c_void_p, C.c_int, C.c_int, C.c_int, C.c_int,
+                             C.POINTER(C.c_double), C.c_void_p]),
+    "tbdk_remap_flow": (C.c_int, [C.c_void_p, C.c_void_p, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, C.c_void_p,
+                                  C.c_int, C.c_int, C.c_int, C.c_void_p, C.c_int, C.c_int, C.c_int, C.c_int,
+                                  C.POINTER(C.c_double), C.c_void_p]),
+    "tbdk_warp_perspective": (C.c_int, [C.c_void_p, C.c_void_p, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, C.c_void_p,
+                                        C.c_int, C.c_int, C.c_int, C.POINTER(C.c_double), C.c_int, C.c_int,
+                                        C.POINTER(C.c_double), C.c_void_p]),
+    "tbdk_warp_perspective_invert": (C.c_int, [C.POINTER(C.c_double), C.POINTER(C.c_double)]),
     "tbdk_tracker_default_args": (C.c_int, [C.POINTER(TrackerArgs)]),
     "tbdk_tracker_create": (C.c_int, [C.POINTER(TrackerArgs), C.POINTER(C.c_void_p)]),
     "tbdk_tracker_destroy": (C.c_int, [C.c_void_p]),

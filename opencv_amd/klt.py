@@ -394,6 +394,125 @@ def warp_affine(src: torch.Tensor, M, dsize, flags: int = INTER_LINEAR, borderMo
     return dst
 
 
+# map kinds of remap (tbdk.h: TBDK_MAP_*)
+MAP_32FC2, MAP_32FC1, MAP_16SC2 = 0, 1, 2
+PIX_U8, PIX_F32 = 0, 2
+
+
+def _rows_packed(t: torch.Tensor) -> bool:
+    """every row contiguous (strides of one-element dimensions carry no meaning)"""
+    return t.numel() == 0 or t[0].is_contiguous()
+
+
+def _pitch(t: torch.Tensor) -> int:
+    """row pitch in bytes"""
+    row = t[0].numel() if t.shape[0] else 0
+    return (t.stride(0) if t.shape[0] > 1 else row) * t.element_size()
+
+
+def _warp_image(t: torch.Tensor, what: str):
+    """(pix, cn) of an (H, W) or (H, W, C) uint8 / float32 device image with packed pixels"""
+    if not t.is_cuda or t.dim() not in (2, 3) or t.dtype not in (torch.uint8, torch.float32):
+        raise _lib.TbdkError(f"{what} expects an (H, W) or (H, W, C) uint8 or float32 device tensor")
+    cn = 1 if t.dim() == 2 else t.shape[2]
+    if not 1 <= cn <= 4 or not _rows_packed(t):
+        raise _lib.TbdkError(f"{what}: 1 to 4 interleaved channels, packed along a row")
+    return (PIX_U8 if t.dtype == torch.uint8 else PIX_F32), cn
+
+
+def _warp_dst(src: torch.Tensor, dst, dh: int, dw: int, what: str) -> torch.Tensor:
+    shape = (dh, dw) if src.dim() == 2 else (dh, dw, src.shape[2])
+    if dst is None:
+        return torch.zeros(shape, dtype=src.dtype, device=src.device)
+    if tuple(dst.shape) != shape or dst.dtype != src.dtype or dst.device != src.device:
+        raise _lib.TbdkError(f"{what}: dst must be a {shape} {src.dtype} tensor on src's device")
+    _warp_image(dst, what)
+    return dst
+
+
+def _border_value(v):
+    a = np.zeros(4, np.float64)
+    v = np.atleast_1d(np.asarray(v, np.float64)).reshape(-1)[:4]
+    a[:len(v)] = v
+    return (C.c_double * 4)(*a)
+
+
+def _image_args(t: torch.Tensor):
+    return t.shape[1], t.shape[0], _pitch(t)
+
+
+def remap(src: torch.Tensor, map1: torch.Tensor, map2: torch.Tensor | None = None, interpolation: int = INTER_LINEAR,
+          borderMode: int = BORDER_CONSTANT, borderValue=0, dst: torch.Tensor | None = None,
+          ctx: Context | None = None, stream=None) -> torch.Tensor:
+    """cv::cuda::remap / cv::remap(src, dst, map1, map2, interpolation, borderMode, borderValue) for
+    CV_8UC1..4 and CV_32FC1..4 with the CPU cv::remap's numerics (bit-exact, whatever the maps hold).
+    map1: (H, W, 2) float32 [CV_32FC2]; (H, W) float32 with map2 (H, W) float32 [CV_32FC1 pair];
+    (H, W, 2) int16 with map2 (H, W) int16/uint16 bits or None [CV_16SC2 (+ CV_16UC1)].  The result has
+    the maps' size.  `dst` may be passed to keep its contents where BORDER_TRANSPARENT skips pixels."""
+    pix, cn = _warp_image(src, "remap")
+    if not map1.is_cuda or (map2 is not None and not map2.is_cuda):
+        raise _lib.TbdkError("remap: device maps")
+    dh, dw = map1.shape[0], map1.shape[1]
+    packed = _rows_packed(map1) and (map2 is None or _rows_packed(map2))
+    if packed and map1.dtype == torch.float32 and map1.dim() == 3 and map1.shape[2] == 2:
+        kind, map2 = MAP_32FC2, None
+    elif packed and map1.dtype == torch.float32 and map1.dim() == 2 and map2 is not None \
+            and map2.dtype == torch.float32 and map2.shape == map1.shape:
+        kind = MAP_32FC1
+    elif packed and map1.dtype == torch.int16 and map1.dim() == 3 and map1.shape[2] == 2 \
+            and (map2 is None or (map2.dtype in (torch.int16, torch.uint16) and map2.shape == map1.shape[:2])):
+        kind = MAP_16SC2
+    else:
+        raise _lib.TbdkError("remap: maps must be CV_32FC2, CV_32FC1 + CV_32FC1, or CV_16SC2 (+ CV_16UC1)")
+    ctx = ctx or Context.get(src.device.index or 0)
+    dst = _warp_dst(src, dst, dh, dw, "remap")
+    _lib.check(ctx.lib.tbdk_remap(ctx.handle, C.c_void_p(src.data_ptr()), pix, cn, *_image_args(src),
+                                  C.c_void_p(dst.data_ptr()), *_image_args(dst), C.c_void_p(map1.data_ptr()),
+                                  _pitch(map1), C.c_void_p(map2.data_ptr()) if map2 is not None else None,
+                                  _pitch(map2) if map2 is not None else 0, kind,
+                                  int(interpolation), int(borderMode), _border_value(borderValue), _stream_ptr(stream)),
+               "tbdk_remap")
+    return dst
+
+
+def remap_flow(src: torch.Tensor, flow: torch.Tensor, sign: int = 1, interpolation: int = INTER_LINEAR,
+               borderMode: int = BORDER_CONSTANT, borderValue=0, dst: torch.Tensor | None = None,
+               ctx: Context | None = None, stream=None) -> torch.Tensor:
+    """Warps `src` by a dense flow without storing a map: remap by (x + sign*flow.x, y + sign*flow.y),
+    byte for byte what remap gives for that float32 map.  flow: (H, W, 2) float32, as
+    FarnebackOpticalFlow.calc and DensePyrLKOpticalFlow.calc return it.  sign=+1 warps frame B onto
+    frame A given the flow A -> B; sign=-1 is warp_flow of the reference's samples/python/opt_flow.py."""
+    pix, cn = _warp_image(src, "remap_flow")
+    if not flow.is_cuda or flow.dtype != torch.float32 or flow.dim() != 3 or flow.shape[2] != 2 \
+            or not _rows_packed(flow):
+        raise _lib.TbdkError("remap_flow: flow must be an (H, W, 2) float32 device tensor")
+    ctx = ctx or Context.get(src.device.index or 0)
+    dst = _warp_dst(src, dst, flow.shape[0], flow.shape[1], "remap_flow")
+    _lib.check(ctx.lib.tbdk_remap_flow(ctx.handle, C.c_void_p(src.data_ptr()), pix, cn, *_image_args(src),
+                                       C.c_void_p(dst.data_ptr()), *_image_args(dst), C.c_void_p(flow.data_ptr()),
+                                       _pitch(flow), int(sign), int(interpolation), int(borderMode),
+                                       _border_value(borderValue), _stream_ptr(stream)), "tbdk_remap_flow")
+    return dst
+
+
+def warp_perspective(src: torch.Tensor, M, dsize, flags: int = INTER_LINEAR, borderMode: int = BORDER_CONSTANT,
+                     borderValue=0, dst: torch.Tensor | None = None, ctx: Context | None = None,
+                     stream=None) -> torch.Tensor:
+    """cv::cuda::warpPerspective(src, dst, M, dsize, flags, borderMode, borderValue) for CV_8UC1..4 and
+    CV_32FC1..4 with the CPU cv::warpPerspective's numerics (bit-exact).  M: 3x3 (host array-like, finite);
+    dsize = (width, height).  Not equal to warp_affine for an affine M: the two round differently,
+    as the reference's two functions do."""
+    pix, cn = _warp_image(src, "warp_perspective")
+    ctx = ctx or Context.get(src.device.index or 0)
+    dst = _warp_dst(src, dst, int(dsize[1]), int(dsize[0]), "warp_perspective")
+    m = (C.c_double * 9)(*[float(v) for v in np.asarray(M, dtype=np.float64).reshape(9)])
+    _lib.check(ctx.lib.tbdk_warp_perspective(ctx.handle, C.c_void_p(src.data_ptr()), pix, cn, *_image_args(src),
+                                             C.c_void_p(dst.data_ptr()), *_image_args(dst), m, int(flags),
+                                             int(borderMode), _border_value(borderValue), _stream_ptr(stream)),
+               "tbdk_warp_perspective")
+    return dst
+
+
 # cv::ColorConversionCodes the front end knows (imgproc.hpp)
 COLOR_BGR2BGRA, COLOR_BGR2GRAY, COLOR_RGB2GRAY = _lib.COLOR_BGR2BGRA, _lib.COLOR_BGR2GRAY, _lib.COLOR_RGB2GRAY
 COLOR_GRAY2BGR, COLOR_BGRA2GRAY, COLOR_RGBA2GRAY = _lib.COLOR_GRAY2BGR, _lib.COLOR_BGRA2GRAY, _lib.COLOR_RGBA2GRAY

@@ -5,7 +5,7 @@ calcOpticalFlowFarneback, HOGDescriptor) on the cases of tests/_reference_cases.
 (goodFeaturesToTrack under a mask: tests/_gftt_mask_cases.py; the corner maps and
 goodFeaturesToTrack on CV_32F images: tests/_gftt_f32_cases.py; cornerSubPix:
 tests/_subpix_cases.py; goodFeaturesToTrack on whole frames:
-tests/_gftt_frame_cases.py)
+tests/_gftt_frame_cases.py; remap and warpPerspective: tests/_remap_cases.py)
 into tests/golden/reference_<op>.npz, through tools/reference_driver.cpp (how to
 build it: tools/record_reference_cases.md).
 
@@ -16,7 +16,8 @@ runtime dispatch) and `noavx2` (OPENCV_CPU_DISABLE=AVX2,AVX512_SKX in the
 child's environment only).  The driver prints checkHardwareSupport; a run whose
 flags do not show the intended state is an error, so a host without AVX2 cannot
 record.  Where the two recordings are byte-identical one copy is stored
-(state "both"); this is asserted for the pyramid, PyrLK and warpAffine.  Where
+(state "both"); this is asserted for the pyramid, PyrLK, warpAffine, remap and
+warpPerspective.  Where
 they differ, the state the oracle models is stored in full, and for the other
 one: whether the integer-valued results were equal (and those results where
 they were not), the share of equal 32-bit words and the largest absolute
@@ -43,13 +44,15 @@ import _gftt_f32_cases as FC  # noqa: E402
 import _subpix_cases as SC  # noqa: E402
 import _gftt_frame_cases as WC  # noqa: E402
 import _klt_tracker_oracle as KT  # noqa: E402
+import _remap_cases as PC  # noqa: E402
 
 LIMIT = 256 * 1024
 STATES = ("default", "noavx2")
 # the state each oracle file models where the two differ (README, numerics)
 MODELLED = {"pyramid": "both", "pyrlk": "both", "warpaffine": "both", "gftt": "noavx2", "gftt_mask": "noavx2",
             "cornermaps": "noavx2", "gftt_f32": "noavx2", "subpix": "both", "gftt_frame": "noavx2",
-            "circle": "both", "farneback": "noavx2", "farneback_box": "noavx2", "hog": "default"}
+            "circle": "both", "remap": "both", "warpperspective": "both", "farneback": "noavx2",
+            "farneback_box": "noavx2", "hog": "default"}
 
 
 class Driver:
@@ -311,6 +314,39 @@ def rec_warpaffine(d):
     return cases, dict(meta=np.array(meta, np.int32), M=np.array(mats, np.float64))
 
 
+def _bv_kw(bv):
+    return {f"bv{k}": float(v) for k, v in enumerate(bv)}
+
+
+def rec_remap(d):
+    """remap into a pre-filled destination (tests/_remap_cases.py: remap_cases)"""
+    cases = []
+    for i, (depth, cn, s, dd, gen, kind, inter, border) in enumerate(PC.remap_cases()):
+        src, dst, m1, m2, _, bv = PC.remap_inputs(i)
+        files = dict(a=src, dst=dst, m1=m1)
+        if m2 is not None:
+            files["m2"] = m2
+        _, rd = d.run("remap", files, w=src.shape[1], h=src.shape[0], cn=cn, depth=depth, dw=dst.shape[1],
+                      dh=dst.shape[0], kind=kind.rstrip("f") if kind.startswith("16") else kind, inter=inter,
+                      border=border, **_bv_kw(bv))
+        out = rd("w", dst.dtype).reshape(dst.shape)
+        cases.append((dict(w=out), {}) if depth == "8u" else ({}, dict(w=out)))
+    return cases, {}
+
+
+def rec_warpperspective(d):
+    """warpPerspective into a pre-filled destination, and invert(M) (tests/_remap_cases.py: persp_cases)"""
+    cases = []
+    for i, (depth, cn, s, dd, name, flags, border) in enumerate(PC.persp_cases()):
+        src, dst, M, bv = PC.persp_inputs(i)
+        _, rd = d.run("warpperspective", dict(a=src, dst=dst, m=M), w=src.shape[1], h=src.shape[0], cn=cn, depth=depth,
+                      dw=dst.shape[1], dh=dst.shape[0], flags=flags, border=border, **_bv_kw(bv))
+        out = rd("w", dst.dtype).reshape(dst.shape)
+        minv = rd("minv", np.float64)
+        cases.append((dict(w=out), dict(minv=minv)) if depth == "8u" else ({}, dict(w=out, minv=minv)))
+    return cases, {}
+
+
 def rec_farneback(d, table=None):
     cases, meta = [], []
     for w, h, ps, pn, ws, flags, use_init in table or RC.FB_CASES:
@@ -410,12 +446,14 @@ def merge(op, rec, whole_limit):
 
 RECORDERS = {"pyramid": rec_pyramid, "pyrlk": rec_pyrlk, "gftt": rec_gftt, "gftt_mask": rec_gftt_mask,
              "cornermaps": rec_cornermaps, "gftt_f32": rec_gftt_f32, "subpix": rec_subpix, "gftt_frame": rec_gftt_frame,
-             "circle": rec_circle, "warpaffine": rec_warpaffine, "farneback": rec_farneback, "farneback_box": rec_farneback_box,
+             "circle": rec_circle, "warpaffine": rec_warpaffine, "remap": rec_remap,
+             "warpperspective": rec_warpperspective, "farneback": rec_farneback, "farneback_box": rec_farneback_box,
              "hog": rec_hog}
 # bytes up to which an output is stored whole (tests/_reference_cases.py: WHOLE_LIMIT).  The kernels are
 # compared with the box Farneback flows within a tolerance, so all six stay whole (about 7 KB under LIMIT)
 WHOLE = {"farneback": 20480, "farneback_box": 72800, "pyrlk": 1 << 20, "gftt": 1 << 20, "gftt_mask": 1 << 20,
-         "hog": 16384, "subpix": 1 << 20, "gftt_frame": 1 << 20}
+         "hog": 16384, "subpix": 1 << 20, "gftt_frame": 1 << 20, "remap": PC.WHOLE_LIMIT,
+         "warpperspective": PC.WHOLE_LIMIT}
 # (gftt_f32: maps above RC.WHOLE_LIMIT as row CRCs; its corner lists are far below it)
 
 
@@ -450,6 +488,10 @@ def case_label(op, i):
         return SC.label(i)
     if op == "gftt_frame":
         return WC.label(i)
+    if op == "remap":
+        return PC.remap_label(i)
+    if op == "warpperspective":
+        return PC.persp_label(i)
     if op == "circle":
         return "centre ({}, {}) radius {}".format(*KT.CIRCLE_CASES[i])
     if op == "cornermaps":

@@ -6,7 +6,8 @@
 //   reference_driver <op> <out-prefix> key=value ...
 //
 // Images are raw 8-bit files (rows of w * cn bytes), or, for gftt and cmap with
-// depth=32f, raw float32 files of one channel; every output goes to
+// depth=32f, raw float32 files of one channel (remap and warpperspective:
+// depth=32f with cn channels, and raw maps); every output goes to
 // <out-prefix>.<name> as raw little-endian data.  The first line printed is the
 // runtime dispatch state, "SSE4_1=. AVX=. AVX2=. FMA3=."; the caller checks it.
 //
@@ -22,6 +23,14 @@
 //   fb    a= b= w= h= ps= lv= ws= it= pn= sg= flags= [init=]               -> f (f32 pairs)
 //   hoggrad a= w= h= cn= gamma= signed=            -> g (f32 pairs), qa (u8 pairs)
 //   hogdet  a= w= h= cn= win=64|48 hit= group=     -> loc (i32 pairs), wt (f64), r (i32 x4), rw (f64), svm (f32)
+//   remap a= w= h= cn= depth=8u|32f dst= dw= dh= kind=32fc2|32fc1|16sc2 m1= [m2=] inter= border= bv0= bv1= bv2= bv3=
+//                                                  -> w (the image's type): remap into the pre-filled destination.
+//                                                  m1: CV_32FC2, CV_32FC1 or CV_16SC2; m2: CV_32FC1 or CV_16UC1.  A 1x1
+//                                                  INTER_LINEAR remap runs first: initInterTab2D fills NNDeltaTab_i on the
+//                                                  first interpolating call of a process, and INTER_NEAREST with a
+//                                                  fraction plane reads it
+//   warpperspective a= w= h= cn= depth= m= (9 doubles, raw) dst= dw= dh= flags= border= bv0..bv3=
+//                                                  -> w (the image's type), minv (9 doubles): invert(M)
 //   circle  w= h= cx= cy= r=                       -> m (u8): circle(img, (cx, cy), r, Scalar(0), -1) on a 255-filled
 //                                                  CV_8UC1 image (no input image)
 #include <cmath>
@@ -89,9 +98,65 @@ static Mat image_depth(const std::string& key, int w, int h)
     return m;
 }
 
+// the source or destination of remap / warpperspective: CV_8UC(cn) or CV_32FC(cn)
+static Mat image_typed(const std::string& key, int w, int h, int cn)
+{
+    const bool f32 = has("depth") && arg("depth") == "32f";
+    Mat m(h, w, f32 ? CV_32FC(cn) : CV_8UC(cn));
+    rd(arg(key), m.data, (size_t)w * h * m.elemSize());
+    return m;
+}
+
+static Mat raw_mat(const std::string& key, int w, int h, int type)
+{
+    Mat m(h, w, type);
+    rd(arg(key), m.data, (size_t)w * h * m.elemSize());
+    return m;
+}
+
+static int run_warps(const std::string& op, const std::string& out)
+{
+    const int w = iarg("w"), h = iarg("h"), cn = iarg("cn"), dw = iarg("dw"), dh = iarg("dh");
+    Mat a = image_typed("a", w, h, cn), d = image_typed("dst", dw, dh, cn);
+    const uchar* before = d.data;
+    const Scalar bv(darg("bv0"), darg("bv1"), darg("bv2"), darg("bv3"));
+    if (op == "remap") {
+        const std::string kind = arg("kind");
+        Mat m1, m2;
+        if (kind == "32fc2") {
+            m1 = raw_mat("m1", dw, dh, CV_32FC2);
+        } else if (kind == "32fc1") {
+            m1 = raw_mat("m1", dw, dh, CV_32FC1);
+            m2 = raw_mat("m2", dw, dh, CV_32FC1);
+        } else if (kind == "16sc2") {
+            m1 = raw_mat("m1", dw, dh, CV_16SC2);
+            if (has("m2")) m2 = raw_mat("m2", dw, dh, CV_16UC1);
+        } else {
+            throw std::runtime_error("unknown map kind " + kind);
+        }
+        {
+            Mat s1(1, 1, CV_8UC1, Scalar(0)), d1, mm(1, 1, CV_32FC2, Scalar(0, 0));
+            remap(s1, d1, mm, noArray(), INTER_LINEAR);
+        }
+        remap(a, d, m1, m2, iarg("inter"), iarg("border"), bv);
+    } else {
+        double m[9], mi[9];
+        rd(arg("m"), m, sizeof m);
+        Mat M(3, 3, CV_64F, m), Mi(3, 3, CV_64F, mi);
+        invert(M, Mi);
+        if (Mi.data != (uchar*)mi) throw std::runtime_error("invert reallocated its destination");
+        wr(out, "minv", mi, sizeof mi);
+        warpPerspective(a, d, M, Size(dw, dh), iarg("flags"), iarg("border"), bv);
+    }
+    if (d.data != before) throw std::runtime_error(op + " reallocated the destination");
+    wr(out, "w", d);
+    return 0;
+}
+
 static int run(const std::string& op, const std::string& out)
 {
     const int w = iarg("w"), h = iarg("h"), cn = has("cn") ? iarg("cn") : 1;
+    if (op == "remap" || op == "warpperspective") return run_warps(op, out);
     if (op == "circle") {
         Mat m(h, w, CV_8UC1, Scalar(255));
         circle(m, Point(iarg("cx"), iarg("cy")), iarg("r"), Scalar(0), -1);
