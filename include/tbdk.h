@@ -277,6 +277,25 @@ int tbdk_timing_select(tbdk_ctx* ctx, const char* names);
  * of a measured loop. */
 int tbdk_timing_calls(tbdk_ctx* ctx, const char* name, int64_t* calls);
 
+/* ---- image layout -------------------------------------------------------- */
+
+/* Every entry point that takes an image takes its row pitch in bytes, and a
+ * region of interest of a larger frame, a decoder's padded surface or a pitched
+ * GpuMat-like buffer is passed as it is, with no copy:
+ *   - u8 images, source or destination, 1 to 4 interleaved channels: any
+ *     pointer and any pitch >= width * cn.  Nothing has to be aligned; the
+ *     kernels choose their wide loads and stores from the addresses they get and
+ *     fall back to narrower ones.  Bytes of a row beyond width * cn are never
+ *     written, and never read as pixels.
+ *   - u16 / fp16 / fp32 images: pointer and pitch multiples of the element size
+ *     (2 or 4), pitch >= a row.
+ *   - two-value planes (CV_32FC2 flows and gradients, 8 bytes per pixel; the
+ *     HOG bin plane, 2 bytes per pixel): pointer and pitch multiples of the
+ *     pixel size.
+ * A pitch below a row, or one that breaks these rules, is TBDK_EINVAL, and
+ * nothing is enqueued.  Results do not depend on the layout.
+ * tests/test_gpu_views_*.py check this contract entry point by entry point. */
+
 /* ---- pyramids ------------------------------------------------------------ */
 
 /* Allocates a padded pyramid for width x height u8 frames.  The level count
@@ -287,7 +306,8 @@ int tbdk_pyr_create(tbdk_ctx* ctx, int width, int height, int max_level,
 int tbdk_pyr_destroy(tbdk_ctx* ctx, tbdk_pyr* pyr);
 
 /* Builds every level of `pyr` (and its derivative planes) from the device u8
- * image `img` (row pitch in bytes).  Replaces cv::buildOpticalFlowPyramid (video/src/lkpyramid.cpp:697)
+ * image `img` (row pitch in bytes; any pointer, any pitch >= width * cn: "image
+ * layout" above).  Replaces cv::buildOpticalFlowPyramid (video/src/lkpyramid.cpp:697)
  * and, level by level, cv::cuda::pyrDown
  * (modules/cudawarping/include/opencv2/cudawarping.hpp:201) — bit-exact with
  * the CPU pyrDown_<FixPtCast<uchar,8>> (imgproc/src/pyramids.cpp:722-857). */
@@ -308,7 +328,10 @@ int tbdk_pyr_create_levels(tbdk_ctx* ctx, int width, int height, int max_level, 
  * (lkpyramid.cpp:726-740) by coordinates, with the same results as the padded
  * copy; other kernels return TBDK_EINVAL.  The frame must stay valid and
  * unchanged while the pyramid is read; the next tbdk_pyr_build gives the
- * pyramid its own level 0 again.  Levels are as tbdk_pyr_build's, bit for bit. */
+ * pyramid its own level 0 again.  Levels are as tbdk_pyr_build's, bit for bit.
+ * Any pointer and any pitch >= width: level 0 keeps the frame's pointer and
+ * pitch (pad 0), and PyrLK bounds its reads by them.  TBDK_EINVAL under ctx
+ * option pyr_fuse 0 (the one-launch-per-level build has no borrowed form). */
 int tbdk_pyr_build_borrowed(tbdk_ctx* ctx, const uint8_t* img, int pitch, tbdk_pyr* pyr, void* stream);
 
 /* Multi-channel frames (cv::cuda::SparsePyrLKOpticalFlow takes 1, 3 or 4
@@ -375,7 +398,8 @@ int tbdk_pyr_download(tbdk_ctx* ctx, const tbdk_pyr* pyr, int level, uint8_t* ho
 int tbdk_pyr_download_deriv(tbdk_ctx* ctx, const tbdk_pyr* pyr, int level, int16_t* host, int host_pitch);
 
 /* Single-level cv::cuda::pyrDown replacement: dst = pyrDown(src),
- * dst size ((w+1)/2, (h+1)/2), plain (unpadded) device images. */
+ * dst size ((w+1)/2, (h+1)/2), plain (unpadded) device images: any pointers,
+ * src_pitch >= w, dst_pitch >= (w+1)/2. */
 int tbdk_pyr_down_u8(tbdk_ctx* ctx, const uint8_t* src, int width, int height, int src_pitch,
                      uint8_t* dst, int dst_pitch, void* stream);
 
@@ -698,7 +722,9 @@ int tbdk_box_propagate_ransac(tbdk_ctx* ctx, const float* prev_pts, const float*
  * for CV_8UC1, with the numerics of the CPU cv::warpAffine
  * (imgproc/src/imgwarp.cpp:2572-2682: 10-bit fixed-point map, 5-bit sub-pixel
  * table, 15-bit bilinear weights) — bit-exact with it.
- *   src, dst : device u8 images (row pitch in bytes); dst must not alias src
+ *   src, dst : device u8 images (row pitch in bytes; any pointers, any pitches
+ *              >= the widths; bytes of dst beyond dst_width in a row are not
+ *              written); dst must not alias src
  *   M        : HOST 2x3 row-major double matrix (dst <- src unless
  *              TBDK_WARP_INVERSE_MAP, then dst -> src, as in the reference)
  *   flags    : TBDK_INTER_NEAREST / LINEAR / CUBIC / AREA | TBDK_WARP_INVERSE_MAP
@@ -832,9 +858,11 @@ int tbdk_farneback_levels(int width, int height, const tbdk_farneback_params* p,
 /* Replaces cv::cuda::FarnebackOpticalFlow::calc(I0, I1, flow, stream)
  * (cudaoptflow/src/farneback.cpp:164-196) with the numerics of the CPU
  * cv::calcOpticalFlowFarneback (video/src/optflowgf.cpp:1096-1190).
- *   prev, next : device u8 frames (width x height, row pitch in bytes)
+ *   prev, next : device u8 frames (width x height) sharing one row pitch in
+ *                bytes: any pointers, any pitch >= width
  *   flow       : device CV_32FC2 output, interleaved (dx, dy) per pixel,
- *                flow_pitch in bytes (multiple of 8); with
+ *                8-byte aligned, flow_pitch in bytes (a multiple of 8, >=
+ *                8 * width; bytes beyond a row are not written); with
  *                TBDK_OPTFLOW_USE_INITIAL_FLOW also the input: the coarsest
  *                level starts from its INTER_AREA resize times the level scale
  *                (optflowgf.cpp:1151-1157)
@@ -845,8 +873,9 @@ int tbdk_farneback(tbdk_ctx* ctx, const uint8_t* prev, const uint8_t* next, int 
 
 /* Stage entry points of tbdk_farneback (parity tests):
  * level image = resize(GaussianBlur(float(img), (smooth_size, smooth_size), sigma),
- * (dst_width, dst_height), INTER_LINEAR) (optflowgf.cpp:1170-1172); dst device
- * float plane, dst_pitch in bytes. */
+ * (dst_width, dst_height), INTER_LINEAR) (optflowgf.cpp:1170-1172); img: any
+ * pointer, pitch >= width; dst device float plane, dst_pitch in bytes (a
+ * multiple of 4, >= 4 * dst_width). */
 int tbdk_fb_level_image(tbdk_ctx* ctx, const uint8_t* img, int width, int height, int pitch, int dst_width,
                         int dst_height, int smooth_size, double sigma, float* dst, int dst_pitch, void* stream);
 /* FarnebackPolyExp (optflowgf.cpp:116-202): src device float plane; dst = 5
@@ -887,7 +916,9 @@ int tbdk_hog_descriptor_size(const tbdk_hog_params* p, int* size);
  * (cudaobjdetect/src/hog.cpp:415-470) with HOGDescriptor::detectMultiScale(img,
  * rects, weights, hit_threshold, win_stride, Size(), scale0, group_threshold)
  * (objdetect/src/hog.cpp:2051-2105), the CPU call of samples/gpu/tbd.cpp:603-605.
- *   img     : device u8 image, cn 1 (gray), 3 (BGR) or 4 (BGRA, alpha ignored)
+ *   img     : device u8 image, cn 1 (gray), 3 (BGR) or 4 (BGRA, alpha ignored);
+ *             any pointer, any pitch >= width * cn (tbdk_hog_detect, _resize and
+ *             _gradient alike)
  *   svm     : host float coefficients, svm_len = descriptor size (+ 1 bias)
  *   rects   : host int32 (x, y, w, h) x max_rects; weights: host double x max_rects
  *   nrects  : number of grouped, clipped detections (<= max_rects)
@@ -904,11 +935,14 @@ int tbdk_hog_detect(tbdk_ctx* ctx, const uint8_t* img, int width, int height, in
  * gradients, hits). A call on a different stream than the context's previous HOG
  * call first synchronises that previous stream.
  * Stage entry points (parity tests).  resize(src, dst, (dw, dh), INTER_LINEAR_EXACT)
- * of a u8 image (imgproc/src/resize.cpp:732-891): */
+ * of a u8 image (imgproc/src/resize.cpp:732-891); dst: any pointer, dst_pitch >=
+ * dst_width * cn, bytes beyond a row not written: */
 int tbdk_hog_resize(tbdk_ctx* ctx, const uint8_t* src, int width, int height, int pitch, int cn, uint8_t* dst,
                     int dst_width, int dst_height, int dst_pitch, void* stream);
 /* HOGDescriptor::computeGradient (hog.cpp:239-550): grad = 2 floats per pixel
- * (grad_pitch bytes per row), qangle = 2 bytes per pixel (qangle_pitch). */
+ * (grad_pitch bytes per row: a multiple of 8, >= 8 * width, grad 8-byte
+ * aligned), qangle = 2 bytes per pixel (qangle_pitch: even, >= 2 * width,
+ * qangle 2-byte aligned); bytes beyond a row are not written. */
 int tbdk_hog_gradient(tbdk_ctx* ctx, const uint8_t* img, int width, int height, int pitch, int cn,
                       const tbdk_hog_params* params, float* grad, int grad_pitch, uint8_t* qangle,
                       int qangle_pitch, void* stream);

@@ -105,16 +105,32 @@ def gpu_metrics(m):
     return {k: getattr(m, k) for k in METRIC_KEYS}
 
 
-def gpu_inputs(gpu, W, H, N, F, seed, drop):
+FRAME_GUARD = 3  # noise rows between the frames of a pitched buffer (gpu_inputs with a layout)
+
+
+def gpu_inputs(gpu, W, H, N, F, seed, drop, layout=None):
     """The GPU-rendered frames (checked equal to the oracle's rendering), the
     per-frame detections with `drop` of them left out at random, and the
-    oracle's sequence for oracle_run."""
+    oracle's sequence for oracle_run.  With `layout` (a name of
+    tests/_views.py's LAYOUTS) the frames are windows of one noise-filled
+    (F, H + guard, pitch) buffer instead: a common pitch larger than the row,
+    the layout's base offset, guard rows between and around the frames."""
     from opencv_amd import klt, tbd
 
     frames, gt = klt.synth_render(seed, W, H, N, 0, F, ctx=gpu)
     seq = sequence(seed, W, H, N, F, drop)
     ofr, ogt, keep = seq
     assert np.array_equal(frames.cpu().numpy(), ofr) and np.array_equal(gt.numpy(), ogt)
+    if layout is not None:
+        import _views as V
+
+        step = H + FRAME_GUARD
+        tall = np.random.default_rng(seed).integers(0, 256, (F * step - FRAME_GUARD, W), dtype=np.uint8)
+        for f in range(F):
+            tall[f * step:f * step + H] = ofr[f]
+        _, view = V.window(tall, layout, seed, device=frames.device)
+        frames = [view[f * step:f * step + H] for f in range(F)]
+        assert all(np.array_equal(frames[f].cpu().numpy(), ofr[f]) and frames[f].stride(0) > W for f in range(F))
     dets = []
     for f in range(F):
         d = tbd.detections_from_gt(ogt[f])
@@ -143,16 +159,17 @@ class ctx_options:
         return False
 
 
-def run_pair(gpu, W, H, N, F, seed, drop=0.0, cfg=None, options=None):
+def run_pair(gpu, W, H, N, F, seed, drop=0.0, cfg=None, options=None, layout=None):
     """The GPU loop (step with next_frame, then a second loop through
     tbdk_tbd_run) against the oracle pipeline, every frame: metrics equal, the
     same tracks predicted with centres within PRED_TOL, every track row equal.
-    Returns the oracle's activity and the worst prediction error."""
+    Returns the oracle's activity and the worst prediction error.  layout: the
+    frames as pitched windows (gpu_inputs)."""
     import torch
     from opencv_amd import tbd
 
     cfg = dict(cfg or {})
-    frames, dets, seq = gpu_inputs(gpu, W, H, N, F, seed, drop)
+    frames, dets, seq = gpu_inputs(gpu, W, H, N, F, seed, drop, layout)
     ora = oracle_run(W, H, N, F, seed, drop, cfg, seq)
     stats = dict(activity(ora), pred_err=0.0)
     with ctx_options(gpu, options):
