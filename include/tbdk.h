@@ -353,7 +353,16 @@ int tbdk_pyr_create_cn(tbdk_ctx* ctx, int width, int height, int cn, int max_lev
  * tbdk_pyr_build_f16 from an fp16 frame (pitch in bytes).  Levels follow
  * pyrDown_<FltCast<float,8>> (imgproc/src/pyramids.cpp:722-857) in fp32,
  * rounded to fp16; tbdk_lk_sparse on two such pyramids runs LKTrackerInvoker's
- * algorithm in fp32. */
+ * algorithm in fp32.
+ * Finite domain: a derivative is at most 16 times the largest pixel step, so
+ * the fp16 planes are finite for pixel values <= 4094 (16 * 4094 = 65504, the
+ * largest finite fp16); 12-bit white (4095) at a hard edge already rounds to
+ * an infinity.  Beyond that the levels and planes are still the rounded values
+ * (infinities included), and tbdk_lk_sparse returns status 0 for every point
+ * whose window position stops being finite: a NaN or infinite position fails
+ * the bounds gate like a position outside the level.  No point comes back with
+ * status 1 and a non-finite next_pts or err; the next_pts of such a status-0
+ * point may be NaN. */
 int tbdk_pyr_create_f16(tbdk_ctx* ctx, int width, int height, int max_level,
                         int win_w, int win_h, tbdk_pyr* pyr);
 int tbdk_pyr_build_f16(tbdk_ctx* ctx, const uint16_t* img, int pitch, tbdk_pyr* pyr, void* stream);
@@ -364,7 +373,13 @@ int tbdk_pyr_build_f16(tbdk_ctx* ctx, const uint16_t* img, int pitch, tbdk_pyr* 
  * fp32 (Ix, Iy) derivative pairs (8 B per pixel), nothing rounded to fp16.
  * tbdk_pyr_build fills it from a u8 frame, tbdk_pyr_build_u16 from a u16
  * frame, tbdk_pyr_build_f32 from an fp32 frame (every conversion exact;
- * pitches in bytes); tbdk_lk_sparse on two such pyramids (impl 0). */
+ * pitches in bytes); tbdk_lk_sparse on two such pyramids (impl 0).
+ * Finite domain: the window sums hold squares of derivatives (16 times a pixel
+ * step) over the window, so they stay finite for pixel values up to about
+ * 1e16 (all of 16U is far inside); above that they overflow and, as on the
+ * fp16 path, a point whose window position stops being finite gets status 0
+ * through the bounds gate, never status 1 with a non-finite result.  Values so
+ * small that the squares underflow (1e-30) fail the min-eigenvalue gate. */
 int tbdk_pyr_create_f32(tbdk_ctx* ctx, int width, int height, int max_level,
                         int win_w, int win_h, tbdk_pyr* pyr);
 int tbdk_pyr_build_u16(tbdk_ctx* ctx, const uint16_t* img, int pitch, tbdk_pyr* pyr, void* stream);

@@ -274,11 +274,20 @@ __global__ __launch_bounds__(64) void lk_cn_kernel(LkArgs a)
                     const int jv = cdescale(q[0] * iw00 + q[cn] * iw01 + q[L.jpitch] * iw10 + q[L.jpitch + cn] * iw11,
                                             W_BITS1 - 5);
                     const int diff = jv - sP[p];
-                    e += diff < 0 ? -diff : diff;
+                    const int ad = diff < 0 ? -diff : diff;
+                    e += ad;
+                    sG[p] = ad;  // (the derivatives have had their last use: level 0, after the iteration)
                 }
-                // the reference adds |diff| in float in window order: equal to the
-                // exact integer sum while that stays below 2^24
-                const float errval = (float)cwave_sum((double)e);
+                // the reference adds |diff| in a float in window order (lkpyramid.cpp:677-692):
+                // the exact sum while that stays within 2^24, where every partial sum is
+                // exact; beyond it each addition rounds, and the same chain is run here
+                const double esum = cwave_sum((double)e);
+                float errval = (float)esum;
+                if (esum > 16777216.0) {  // block-uniform
+                    __syncthreads();
+                    errval = 0.f;
+                    for (int p = 0; p < area; ++p) errval += (float)sG[p];
+                }
                 errv = errval * 1.f / (float)(32 * winW * cn * winH);
             }
         }

@@ -176,7 +176,7 @@ __global__ __launch_bounds__(64) void lk_cn_f32_kernel(LkArgs a)
         prevx -= halfx;
         prevy -= halfy;
         const int ipx = (int)floorf(prevx), ipy = (int)floorf(prevy);
-        if (ipx < -WW || ipx >= L.w || ipy < -WH || ipy >= L.h) {
+        if (lkdev::out_of_level(prevx, prevy, ipx, ipy, WW, WH, L.w, L.h)) {
             if (level == 0) {
                 status = 0;
                 errv = 0.f;
@@ -228,7 +228,7 @@ __global__ __launch_bounds__(64) void lk_cn_f32_kernel(LkArgs a)
         float pdx = 0.f, pdy = 0.f;
         for (int j = 0; j < a.max_count; ++j) {
             const int inx = (int)floorf(nextx), iny = (int)floorf(nexty);
-            if (inx < -WW || inx >= L.w || iny < -WH || iny >= L.h) {
+            if (lkdev::out_of_level(nextx, nexty, inx, iny, WW, WH, L.w, L.h)) {
                 if (level == 0) status = 0;
                 break;
             }
@@ -274,7 +274,7 @@ __global__ __launch_bounds__(64) void lk_cn_f32_kernel(LkArgs a)
         if (level == 0 && a.err && (a.flags & TBDK_OPTFLOW_LK_GET_MIN_EIGENVALS) == 0 && status) {
             const float npx = outx - halfx, npy = outy - halfy;
             const int inx = (int)floorf(npx), iny = (int)floorf(npy);
-            if (inx < -WW || inx >= L.w || iny < -WH || iny >= L.h) {
+            if (lkdev::out_of_level(npx, npy, inx, iny, WW, WH, L.w, L.h)) {
                 status = 0;
             } else {
                 a_ = npx - inx;

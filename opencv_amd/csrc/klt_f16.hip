@@ -424,7 +424,7 @@ __global__ __launch_bounds__(64, (!F32 && WW <= 21) ? TBDK_LK16_MINW : 1) void l
         prevy -= halfy;
         const int ipx = (int)floorf(prevx), ipy = (int)floorf(prevy);
         bool act = valid;
-        if (ipx < -WW || ipx >= L.w || ipy < -WH || ipy >= L.h) {
+        if (out_of_level(prevx, prevy, ipx, ipy, WW, WH, L.w, L.h)) {
             if (level == 0) {
                 status = 0;
                 errv = 0.f;
@@ -474,7 +474,7 @@ __global__ __launch_bounds__(64, (!F32 && WW <= 21) ? TBDK_LK16_MINW : 1) void l
                 a22 = __builtin_fmaf(gy[r], gy[r], a22);
             }
             {
-                const bool jin = act && !(pinx < -WW || pinx >= L.w || piny < -WH || piny >= L.h);
+                const bool jin = act && !out_of_level(nextx, nexty, pinx, piny, WW, WH, L.w, L.h);
                 const uint32_t joff = jin ? (uint32_t)((piny + L.jpad) * L.jpitch + (pinx + x + L.jpad) * VB) : 0u;
 #pragma unroll
                 for (int r = 0; r <= WH; ++r) jp[r] = PX::ld(rJ, joff, r * L.jpitch);
@@ -499,7 +499,7 @@ __global__ __launch_bounds__(64, (!F32 && WW <= 21) ? TBDK_LK16_MINW : 1) void l
         for (int j = 0; j < a.max_count; ++j) {
             if (!any_lane(act)) break;
             const int inx = (int)floorf(nextx), iny = (int)floorf(nexty);
-            if (act && (inx < -WW || inx >= L.w || iny < -WH || iny >= L.h)) {
+            if (act && out_of_level(nextx, nexty, inx, iny, WW, WH, L.w, L.h)) {
                 if (level == 0) status = 0;
                 act = false;
             }
@@ -548,7 +548,7 @@ __global__ __launch_bounds__(64, (!F32 && WW <= 21) ? TBDK_LK16_MINW : 1) void l
             bool want = valid && status;
             const float npx = outx - halfx, npy = outy - halfy;
             const int inx = (int)floorf(npx), iny = (int)floorf(npy);
-            if (want && (inx < -WW || inx >= L.w || iny < -WH || iny >= L.h)) {
+            if (want && out_of_level(npx, npy, inx, iny, WW, WH, L.w, L.h)) {
                 status = 0;
                 want = false;
             }

@@ -238,7 +238,9 @@
                     const int jv = descale(q[0] * iw00 + q[1] * iw01 + q[L.jpitch] * iw10 + q[L.jpitch + 1] * iw11,
                                            W_BITS1 - 5);
                     const int diff = jv - sP[p];
-                    e += diff < 0 ? -diff : diff;
+                    const int ad = diff < 0 ? -diff : diff;
+                    e += ad;
+                    sG[p] = ad;  // (the derivatives have had their last use: level 0, after the iteration)
                     px += qx;
                     py += qy;
                     if (px >= winW) {
@@ -246,7 +248,16 @@
                         py += 1;
                     }
                 }
-                const float errval = (float)wave_sum((double)e);
+                // the reference adds |diff| in a float in window order (lkpyramid.cpp:677-692):
+                // the exact sum while that stays within 2^24, where every partial sum is
+                // exact; beyond it each addition rounds, and the same chain is run here
+                const double esum = wave_sum((double)e);
+                float errval = (float)esum;
+                if (esum > 16777216.0) {  // block-uniform
+                    __syncthreads();
+                    errval = 0.f;
+                    for (int p = 0; p < area; ++p) errval += (float)sG[p];
+                }
                 errv = errval * 1.f / (float)(32 * winW * winH);
             }
         }

@@ -121,5 +121,14 @@ __device__ __forceinline__ uint32_t pair_sel(uint32_t off)
     return 0x0C000C00u | ((off & 3u) + (((off & 3u) + 1u) << 16));
 }
 
+// the bounds gate of the float pixel paths: a window origin (ix, iy) =
+// floor(fx, fy) outside [-win, size).  A NaN coordinate converts to 0, which is
+// inside every level, so it is named here: a non-finite position fails the
+// gate (+-Inf saturate to INT_MAX / INT_MIN and fail by the range)
+__device__ __forceinline__ bool out_of_level(float fx, float fy, int ix, int iy, int ww, int wh, int w, int h)
+{
+    return fx != fx || fy != fy || ix < -ww || ix >= w || iy < -wh || iy >= h;
+}
+
 }  // namespace lkdev
 }  // namespace tbdk

@@ -207,6 +207,18 @@ static inline float bil(const float* w, float v00, float v01, float v10, float v
     return fmaf(w[3], v11, t);
 }
 
+/* The bounds gate: the window origin floor(fx, fy) outside [-win, size).  A
+ * non-finite position fails it (status 0 at level 0, the iteration ends); the
+ * test is made on the floats, so nothing non-finite or out of int's range is
+ * ever converted.  For every other position this is the reference's integer
+ * comparison (lkpyramid.cpp:219-226, 262-268): floorf's value is integral, and
+ * integral floats compare with the bounds as the converted ints do. */
+static inline int out_of_level(float fx, float fy, int WW, int WH, int w, int h)
+{
+    const float x = floorf(fx), y = floorf(fy);
+    return !(x >= (float)-WW && x < (float)w && y >= (float)-WH && y < (float)h);
+}
+
 typedef struct orc16_job {
     const orc16_pyr *prev, *next;
     const float* prevPts;
@@ -262,14 +274,14 @@ static void lk16_point(const orc16_job* jb, int i, float* buf)
         outy = nexty;
         prevx -= halfx;
         prevy -= halfy;
-        const int ipx = (int)floorf(prevx), ipy = (int)floorf(prevy);
-        if (ipx < -WW || ipx >= I->w || ipy < -WH || ipy >= I->h) {
+        if (out_of_level(prevx, prevy, WW, WH, I->w, I->h)) {
             if (level == 0) {
                 status = 0;
                 errv = 0.f;
             }
             continue;
         }
+        const int ipx = (int)floorf(prevx), ipy = (int)floorf(prevy);
         float w[4];
         weights16(prevx - ipx, prevy - ipy, w);
         float s[3];
@@ -310,11 +322,11 @@ static void lk16_point(const orc16_job* jb, int i, float* buf)
         nexty -= halfy;
         float pdx = 0.f, pdy = 0.f;
         for (int j = 0; j < jb->maxCount; ++j) {
-            const int inx = (int)floorf(nextx), iny = (int)floorf(nexty);
-            if (inx < -WW || inx >= J->w || iny < -WH || iny >= J->h) {
+            if (out_of_level(nextx, nexty, WW, WH, J->w, J->h)) {
                 if (level == 0) status = 0;
                 break;
             }
+            const int inx = (int)floorf(nextx), iny = (int)floorf(nexty);
             ++nit;
             weights16(nextx - inx, nexty - iny, w);
             float b[2];
@@ -352,10 +364,10 @@ static void lk16_point(const orc16_job* jb, int i, float* buf)
         }
         if (level == 0 && jb->err && (flags & ORC_OPTFLOW_LK_GET_MIN_EIGENVALS) == 0 && status) {
             const float npx = outx - halfx, npy = outy - halfy;
-            const int inx = (int)floorf(npx), iny = (int)floorf(npy);
-            if (inx < -WW || inx >= J->w || iny < -WH || iny >= J->h) {
+            if (out_of_level(npx, npy, WW, WH, J->w, J->h)) {
                 status = 0;
             } else {
+                const int inx = (int)floorf(npx), iny = (int)floorf(npy);
                 weights16(npx - inx, npy - iny, w);
                 for (int e = 0; e < WE; ++e) {
                     const int x = e / cn, ch = e - x * cn;
