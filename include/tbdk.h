@@ -78,7 +78,7 @@ typedef struct tbdk_pyr {
                                         (Ix_c, Iy_c) pairs for c = 0..cn-1 */
 } tbdk_pyr;
 
-#define TBDK_ABI_VERSION 2
+#define TBDK_ABI_VERSION 3   /* 3: tbdk_homography_params, tbdk_homography and tbdk_find_homography */
 #define TBDK_PYR_NO_DERIVS 1
 
 /* cv::TermCriteria(COUNT+EPS, maxCount, epsilon) + flags + minEigThreshold of
@@ -715,6 +715,62 @@ int tbdk_box_propagate_ransac(tbdk_ctx* ctx, const float* prev_pts, const float*
                               const tbdk_ransac_params* params, tbdk_box_fit* out, int32_t* iters, uint8_t* inliers,
                               void* stream);
 
+/* ---- findHomography --------------------------------------------------------- */
+
+#define TBDK_HOMOGRAPHY_LSQ 0      /* method 0: all pairs */
+#define TBDK_HOMOGRAPHY_RANSAC 8   /* cv::RANSAC */
+#define TBDK_HOMOGRAPHY_MAX_PAIRS 4096  /* status != 0 pairs of one set the kernel holds */
+typedef struct tbdk_homography_params {
+    int32_t method;                /* 0 or 8; 4 (LMEDS) and 16 (RHO) are TBDK_EINVAL */
+    double  reproj_threshold;      /* <= 0 means 3, as the reference */
+    int32_t max_iters;             /* 1..10000, reference default 2000 */
+    double  confidence;            /* (0, 1), reference default 0.995 */
+    int32_t refine;                /* 1: the reference's LM step; 0: stop before it */
+} tbdk_homography_params;
+typedef struct tbdk_homography {
+    double  h[9];                  /* row-major, h[8] == 1; identity when !valid */
+    int32_t npoints;               /* status != 0 pairs; -1 over the cap */
+    int32_t ninliers;              /* consensus size (npoints for method 0) */
+    int32_t iters;                 /* RANSAC iterations the reference's loop would have run */
+    int32_t valid;                 /* the reference returned a non-empty H */
+} tbdk_homography;
+/* method RANSAC, threshold 3, 2000 iterations, confidence 0.995, refine 1 */
+int tbdk_homography_default_params(tbdk_homography_params* p);
+
+/* Batched cv::findHomography(src, dst, method, reproj_threshold, mask, max_iters,
+ * confidence) on point sets (calib3d/src/fundam.cpp:350-433), one workgroup
+ * per set, nothing on the host: method 0 fits all pairs, RANSAC runs the
+ * reference's loop (its cv::RNG sequence seeded per set, getSubset's redraws and
+ * checkSubset, the normalised 4-point DLT with the reference's Jacobi, the float
+ * reprojection error, the strict "first best model wins" rule and
+ * RANSACUpdateNumIters), re-fits on the inliers in point order and, with
+ * refine = 1, runs the reference's 10-iteration LM step.
+ *   src_pts, dst_pts : device float pairs; set i is [offsets[i], offsets[i+1])
+ *   status           : device u8 per pair or NULL; status == 0 pairs are dropped
+ *                      by an in-order compaction before anything else
+ *   offsets          : nsets + 1 device int32 values, as tbdk_box_propagate
+ *   out[i]           : device; see tbdk_homography.  A set with fewer than 4
+ *                      pairs, with no acceptable subset in iteration 0, or
+ *                      without consensus has valid = 0 and the identity.  Method
+ *                      0 with fewer than 4 pairs gives valid = 0 too (the
+ *                      reference returns a meaningless matrix there).  A set
+ *                      with more than TBDK_HOMOGRAPHY_MAX_PAIRS status != 0 pairs
+ *                      is never truncated: npoints = -1, valid = 0
+ *   mask             : device u8 per pair or NULL: 1 for the inliers (every
+ *                      status != 0 pair for method 0 and for 4 pairs), 0 for
+ *                      outliers, status == 0 pairs and sets without a result;
+ *                      every byte is written once
+ * With refine = 0, ninliers, iters, the mask and h are the reference's bit for
+ * bit (RANSACUpdateNumIters' log and pow aside); the refined h
+ * agrees with the reference's in what it does to the inlier points.  Points
+ * that are NaN or infinite leave the call bounded; what h they give is
+ * unspecified.  Asynchronous on `stream`, no allocation, no host
+ * synchronisation; nsets == 0 is a no-op.  TBDK_EINVAL for parameters out of
+ * range.  Timed as kernel "find_homography". */
+int tbdk_find_homography(tbdk_ctx* ctx, const float* src_pts, const float* dst_pts, const uint8_t* status,
+                         const int32_t* offsets, int nsets, const tbdk_homography_params* params,
+                         tbdk_homography* out, uint8_t* mask, void* stream);
+
 /* ---- affine warp ------------------------------------------------------------ */
 
 /* interpolation flags / border modes: the reference's values
@@ -805,6 +861,19 @@ int tbdk_remap_flow(tbdk_ctx* ctx, const void* src, int pix, int cn, int src_wid
 int tbdk_warp_perspective(tbdk_ctx* ctx, const void* src, int pix, int cn, int src_width, int src_height,
                           int src_pitch, void* dst, int dst_width, int dst_height, int dst_pitch, const double* M,
                           int flags, int border, const double* border_value, void* stream);
+
+/* tbdk_warp_perspective with the matrix in DEVICE memory, for a matrix an earlier call on the same
+ * stream produced (&out[i].h[0] of tbdk_find_homography): no host round trip between the two.
+ *   M     : device pointer to 9 doubles, 8-byte aligned; read when the kernel runs.  It is inverted
+ *           on the device with tbdk_warp_perspective_invert's arithmetic, so for the same matrix
+ *           the result is byte-identical to tbdk_warp_perspective
+ *   valid : device int32 or NULL (&out[i].valid).  Where it reads 0, or an entry of M is not
+ *           finite (tbdk_warp_perspective returns TBDK_EINVAL there; this call cannot know), dst
+ *           is left untouched
+ * Timing name "warp_perspective_dev". */
+int tbdk_warp_perspective_dev(tbdk_ctx* ctx, const void* src, int pix, int cn, int src_width, int src_height,
+                              int src_pitch, void* dst, int dst_width, int dst_height, int dst_pitch, const double* M,
+                              const int32_t* valid, int flags, int border, const double* border_value, void* stream);
 
 /* The host-side inverse tbdk_warp_perspective takes (cv::invert's 3x3 CV_64F branch), exported
  * for the tests; host only, needs no GPU */

@@ -694,6 +694,47 @@ inline void warpPerspective(Context& ctx, const GpuMatView& src, GpuMatView& dst
           "tbdk_warp_perspective");
 }
 
+// The same with M in DEVICE memory (nine doubles, e.g. &H[i].h[0] of
+// findHomography below, produced earlier on the same stream): the overload is
+// named, since a host and a device pointer have one type.  valid: an optional
+// device int32 (&H[i].valid); where it reads 0 dst is left untouched.
+inline void warpPerspectiveDeviceMatrix(Context& ctx, const GpuMatView& src, GpuMatView& dst, const double* deviceM,
+                                        const int32_t* deviceValid = nullptr, int flags = TBDK_INTER_LINEAR,
+                                        int borderMode = TBDK_BORDER_CONSTANT, const Scalar& borderValue = Scalar(),
+                                        void* stream = nullptr)
+{
+    const int pix = detail::warp_pix(src, dst, "warpPerspective");
+    check(tbdk_warp_perspective_dev(ctx.get(), src.data, pix, src.cn, src.width, src.height, src.pitch, dst.data,
+                                    dst.width, dst.height, dst.pitch, deviceM, deviceValid, flags, borderMode,
+                                    borderValue.val, stream),
+          "tbdk_warp_perspective_dev");
+}
+
+// cv::findHomography(srcPoints, dstPoints, method, ransacReprojThreshold, mask,
+// maxIters, confidence) (calib3d.hpp) on device point sets, batched as
+// estimateRigidTransform above: set i is pairs [offsets[i], offsets[i + 1]) of
+// src -> dst (device float2 arrays), status a device u8 mask or nullptr.  out
+// (device, nsets entries) gets H row-major with valid = 0 and the identity where
+// the reference returns an empty Mat; mask (device u8 per pair, or nullptr) the
+// inliers.  method is 0 or RANSAC (8).  Nothing is copied to the host
+// (tbdk_find_homography).
+enum { LSQ = TBDK_HOMOGRAPHY_LSQ, RANSAC = TBDK_HOMOGRAPHY_RANSAC };
+inline void findHomography(Context& ctx, const float* src, const float* dst, const uint8_t* status,
+                           const int32_t* offsets, int nsets, tbdk_homography* out, int method = RANSAC,
+                           double ransacReprojThreshold = 3.0, uint8_t* mask = nullptr, int maxIters = 2000,
+                           double confidence = 0.995, bool refine = true, void* stream = nullptr)
+{
+    tbdk_homography_params p;
+    check(tbdk_homography_default_params(&p), "tbdk_homography_default_params");
+    p.method = method;
+    p.reproj_threshold = ransacReprojThreshold;
+    p.max_iters = maxIters;
+    p.confidence = confidence;
+    p.refine = refine ? 1 : 0;
+    check(tbdk_find_homography(ctx.get(), src, dst, status, offsets, nsets, &p, out, mask, stream),
+          "tbdk_find_homography");
+}
+
 // cv::cornerSubPix(image, corners, winSize, zeroZone, criteria) (imgproc.hpp;
 // imgproc/src/cornersubpix.cpp:44-156; the reference has no CUDA form) on the
 // device, with the CPU function's bits: corners is device memory, nrows x rowCap

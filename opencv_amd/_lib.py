@@ -19,7 +19,7 @@ TBDK_ENOMEM = -3
 TBDK_ENODEV = -4
 TBDK_MAX_LEVELS = 8
 TBDK_PIX_U8, TBDK_PIX_U16, TBDK_PIX_F32 = 0, 1, 2  # include/tbdk.h: pixel types of the *_px entries
-TBDK_ABI_VERSION = 2  # include/tbdk.h: the struct layouts below
+TBDK_ABI_VERSION = 3  # include/tbdk.h: the struct layouts below
 OPTFLOW_USE_INITIAL_FLOW = 4
 OPTFLOW_LK_GET_MIN_EIGENVALS = 8
 
@@ -131,6 +131,16 @@ class BoxFit(C.Structure):
 
 class RansacParams(C.Structure):
     _fields_ = [("max_iters", C.c_int32), ("good_ratio", C.c_double)]
+
+
+class HomographyParams(C.Structure):
+    _fields_ = [("method", C.c_int32), ("reproj_threshold", C.c_double), ("max_iters", C.c_int32),
+                ("confidence", C.c_double), ("refine", C.c_int32)]
+
+
+class Homography(C.Structure):
+    _fields_ = [("h", C.c_double * 9), ("npoints", C.c_int32), ("ninliers", C.c_int32), ("iters", C.c_int32),
+                ("valid", C.c_int32)]
 
 
 class SubpixParams(C.Structure):
@@ -302,6 +312,9 @@ SIGNATURES = {
     "tbdk_box_propagate_ransac": (C.c_int, [C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p,
                                             C.c_int, C.c_int, C.POINTER(RansacParams), C.c_void_p, C.c_void_p,
                                             C.c_void_p, C.c_void_p]),
+    "tbdk_homography_default_params": (C.c_int, [C.POINTER(HomographyParams)]),
+    "tbdk_find_homography": (C.c_int, [C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_int,
+                                       C.POINTER(HomographyParams), C.c_void_p, C.c_void_p, C.c_void_p]),
     "tbdk_warp_affine_u8": (C.c_int, [C.c_void_p, C.c_void_p, C.c_int, C.c_int, C.c_int, C.c_void_p, C.c_int, C.c_int,
                                       C.c_int, C.POINTER(C.c_double), C.c_int, C.c_int, C.c_int, C.c_void_p]),
     # ctx, src, pix, cn, sw, sh, spitch, dst, dw, dh, dpitch, ...
@@ -314,6 +327,9 @@ SIGNATURES = {
     "tbdk_warp_perspective": (C.c_int, [C.c_void_p, C.c_void_p, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, C.c_void_p,
                                         C.c_int, C.c_int, C.c_int, C.POINTER(C.c_double), C.c_int, C.c_int,
                                         C.POINTER(C.c_double), C.c_void_p]),
+    "tbdk_warp_perspective_dev": (C.c_int, [C.c_void_p, C.c_void_p, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int,
+                                            C.c_void_p, C.c_int, C.c_int, C.c_int, C.c_void_p, C.c_void_p, C.c_int,
+                                            C.c_int, C.POINTER(C.c_double), C.c_void_p]),
     "tbdk_warp_perspective_invert": (C.c_int, [C.POINTER(C.c_double), C.POINTER(C.c_double)]),
     "tbdk_tracker_default_args": (C.c_int, [C.POINTER(TrackerArgs)]),
     "tbdk_tracker_create": (C.c_int, [C.POINTER(TrackerArgs), C.POINTER(C.c_void_p)]),

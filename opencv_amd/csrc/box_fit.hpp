@@ -8,6 +8,8 @@
 
 #include <hip/hip_runtime.h>
 
+#include "ransac_rng.hpp"
+
 namespace tbdk {
 
 struct SimilarityFit {
@@ -88,15 +90,7 @@ __device__ inline SimilarityFit wave_fit_similarity(const float2* a, const float
 // scalar registers (the LDS reads of the drawn pairs go through readfirstlane);
 // only the inlier test runs lanes-over-points.
 
-struct RansacRng {
-    unsigned long long state = ~0ull;
-    // core/operations.hpp:383-393: uniform(0, n) = next() % n
-    __device__ __forceinline__ int draw(int n)
-    {
-        state = (unsigned long long)(unsigned)state * 4164903690u + (unsigned)(state >> 32);
-        return (int)((unsigned)state % (unsigned)n);
-    }
-};
+// RansacRng: ransac_rng.hpp
 
 struct RansacFit {
     SimilarityFit fit;  // over the consensus set; ok = 0 without consensus

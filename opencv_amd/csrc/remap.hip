@@ -168,7 +168,7 @@ __device__ __forceinline__ bool sample_pixel(const RemapArgs& a, const rc::Coord
 constexpr int kGroup = 4;  // destination pixels per thread
 
 template <typename T, int CN, int INTER>
-__global__ __launch_bounds__(256) void remap_kernel(RemapArgs a)
+__device__ __forceinline__ void remap_row_group(const RemapArgs& a)
 {
     const int y = blockIdx.y;
     const int x0 = (blockIdx.x * blockDim.x + threadIdx.x) * kGroup;
@@ -200,6 +200,65 @@ __global__ __launch_bounds__(256) void remap_kernel(RemapArgs a)
 #pragma unroll
             for (int j = 0; j < CN; ++j) D[k * CN + j] = out[k * CN + j];
         }
+}
+
+template <typename T, int CN, int INTER>
+__global__ __launch_bounds__(256) void remap_kernel(RemapArgs a)
+{
+    remap_row_group<T, CN, INTER>(a);
+}
+
+// warpPerspective with the matrix in device memory (tbdk_warp_perspective_dev):
+// every thread reads the nine doubles, inverts them unless the caller's matrix
+// already maps dst -> src (rc::invert_3x3, the host path's arithmetic) and runs
+// the same sampling.  A zero *valid or a non-finite entry leaves dst untouched.
+template <typename T, int CN, int INTER>
+__global__ __launch_bounds__(256) void remap_persp_dev_kernel(RemapArgs a, const double* __restrict__ M,
+                                                              const int32_t* __restrict__ valid, int inverse_map)
+{
+    if (valid && *valid == 0) return;
+    double m[9];
+    bool finite = true;
+#pragma unroll
+    for (int i = 0; i < 9; ++i) {
+        m[i] = M[i];
+        finite = finite && isfinite(m[i]);
+    }
+    if (!finite) return;
+    if (inverse_map) {
+#pragma unroll
+        for (int i = 0; i < 9; ++i) a.m[i] = m[i];
+    } else {
+        rc::invert_3x3(m, a.m);
+    }
+    remap_row_group<T, CN, INTER>(a);
+}
+
+template <typename T, int CN>
+hipError_t launch_dev_cn(const RemapArgs& a, int inter, const double* M, const int32_t* valid, int inv, hipStream_t s)
+{
+    const dim3 grid((a.dw + kGroup * 256 - 1) / (kGroup * 256), a.dh), block(256);
+    if (inter == rc::kNearest)
+        hipLaunchKernelGGL((remap_persp_dev_kernel<T, CN, rc::kNearest>), grid, block, 0, s, a, M, valid, inv);
+    else if (inter == rc::kLinear)
+        hipLaunchKernelGGL((remap_persp_dev_kernel<T, CN, rc::kLinear>), grid, block, 0, s, a, M, valid, inv);
+    else if constexpr (sizeof(T) == 1)
+        hipLaunchKernelGGL((remap_persp_dev_kernel<T, CN, rc::kCubic>), grid, block, 0, s, a, M, valid, inv);
+    else
+        return hipErrorInvalidValue;
+    return hipGetLastError();
+}
+
+template <typename T>
+hipError_t launch_dev_t(const RemapArgs& a, int cn, int inter, const double* M, const int32_t* valid, int inv,
+                        hipStream_t s)
+{
+    switch (cn) {
+    case 1: return launch_dev_cn<T, 1>(a, inter, M, valid, inv, s);
+    case 2: return launch_dev_cn<T, 2>(a, inter, M, valid, inv, s);
+    case 3: return launch_dev_cn<T, 3>(a, inter, M, valid, inv, s);
+    default: return launch_dev_cn<T, 4>(a, inter, M, valid, inv, s);
+    }
 }
 
 template <typename T, int CN>
@@ -295,27 +354,8 @@ int run(tbdk_ctx* ctx, const char* name, const Image& im, const RemapArgs& a, in
 
 }  // namespace
 
-// cv::invert, 3x3 CV_64F (core/src/lapack.cpp: det3, d = 1./d), host double
-// arithmetic; a singular matrix gives the zero matrix, as cv::invert leaves it
-void invert_3x3(const double* m, double* out)
-{
-    const double d = m[0] * (m[4] * m[8] - m[5] * m[7]) - m[1] * (m[3] * m[8] - m[5] * m[6]) +
-                     m[2] * (m[3] * m[7] - m[4] * m[6]);
-    double t[9] = {0, 0, 0, 0, 0, 0, 0, 0, 0};
-    if (d != 0.) {
-        const double r = 1. / d;
-        t[0] = (m[4] * m[8] - m[5] * m[7]) * r;
-        t[1] = (m[2] * m[7] - m[1] * m[8]) * r;
-        t[2] = (m[1] * m[5] - m[2] * m[4]) * r;
-        t[3] = (m[5] * m[6] - m[3] * m[8]) * r;
-        t[4] = (m[0] * m[8] - m[2] * m[6]) * r;
-        t[5] = (m[2] * m[3] - m[0] * m[5]) * r;
-        t[6] = (m[3] * m[7] - m[4] * m[6]) * r;
-        t[7] = (m[1] * m[6] - m[0] * m[7]) * r;
-        t[8] = (m[0] * m[4] - m[1] * m[3]) * r;
-    }
-    for (int i = 0; i < 9; ++i) out[i] = t[i];
-}
+// cv::invert, 3x3 CV_64F: remap_core.hpp, shared with the device-matrix kernel
+void invert_3x3(const double* m, double* out) { remap_core::invert_3x3(m, out); }
 
 }  // namespace tbdk
 
@@ -402,6 +442,30 @@ int tbdk_warp_perspective(tbdk_ctx* ctx, const void* src, int pix, int cn, int s
     a.bw0 = rc::perspective_block_width(dst_width, dst_height);
     a.front = kFrontPerspective;
     return run(ctx, "warp_perspective", im, a, inter, stream);
+}
+
+int tbdk_warp_perspective_dev(tbdk_ctx* ctx, const void* src, int pix, int cn, int src_width, int src_height,
+                              int src_pitch, void* dst, int dst_width, int dst_height, int dst_pitch, const double* M,
+                              const int32_t* valid, int flags, int border, const double* border_value, void* stream)
+{
+    const Image im{src, pix, cn, src_width, src_height, src_pitch, dst, dst_width, dst_height, dst_pitch};
+    RemapArgs a;
+    int inter = flags & 7;
+    if (!M || (reinterpret_cast<uintptr_t>(M) & 7) || (reinterpret_cast<uintptr_t>(valid) & 3) ||
+        (flags & ~(7 | TBDK_WARP_INVERSE_MAP)))
+        return TBDK_EINVAL;
+    const int st = prepare(ctx, im, &inter, border, border_value, &a);
+    if (st != TBDK_OK) return st < 0 ? st : TBDK_OK;
+    a.bw0 = rc::perspective_block_width(dst_width, dst_height);
+    a.front = kFrontPerspective;
+    DeviceGuard g(ctx->device);
+    hipStream_t s = static_cast<hipStream_t>(stream);
+    const int inv = (flags & TBDK_WARP_INVERSE_MAP) ? 1 : 0;
+    const int rec = timing_begin(ctx, "warp_perspective_dev", s);
+    const hipError_t e = im.pix == TBDK_PIX_U8 ? launch_dev_t<uint8_t>(a, im.cn, inter, M, valid, inv, s)
+                                               : launch_dev_t<float>(a, im.cn, inter, M, valid, inv, s);
+    timing_end(ctx, rec, s);
+    return e == hipSuccess ? TBDK_OK : (e == hipErrorOutOfMemory ? TBDK_ENOMEM : TBDK_EHIP);
 }
 
 int tbdk_warp_perspective_invert(const double* M, double* out)

@@ -35,6 +35,28 @@ struct Coord {
     int ax, ay;  // 5-bit sub-pixel fractions (0 under NEAREST)
 };
 
+// cv::invert, 3x3 CV_64F (core/src/lapack.cpp: det3, d = 1./d), double
+// arithmetic; a singular matrix gives the zero matrix, as cv::invert leaves it
+TBDK_HD void invert_3x3(const double* m, double* out)
+{
+    const double d = m[0] * (m[4] * m[8] - m[5] * m[7]) - m[1] * (m[3] * m[8] - m[5] * m[6]) +
+                     m[2] * (m[3] * m[7] - m[4] * m[6]);
+    double t[9] = {0, 0, 0, 0, 0, 0, 0, 0, 0};
+    if (d != 0.) {
+        const double r = 1. / d;
+        t[0] = (m[4] * m[8] - m[5] * m[7]) * r;
+        t[1] = (m[2] * m[7] - m[1] * m[8]) * r;
+        t[2] = (m[1] * m[5] - m[2] * m[4]) * r;
+        t[3] = (m[5] * m[6] - m[3] * m[8]) * r;
+        t[4] = (m[0] * m[8] - m[2] * m[6]) * r;
+        t[5] = (m[2] * m[3] - m[0] * m[5]) * r;
+        t[6] = (m[3] * m[7] - m[4] * m[6]) * r;
+        t[7] = (m[1] * m[6] - m[0] * m[7]) * r;
+        t[8] = (m[0] * m[4] - m[1] * m[3]) * r;
+    }
+    for (int i = 0; i < 9; ++i) out[i] = t[i];
+}
+
 TBDK_HD int sat16(int v) { return v < -32768 ? -32768 : (v > 32767 ? 32767 : v); }
 
 // cvRound(float) as cvtss2si: ties to even; 0x80000000 for NaN and values outside int

@@ -365,6 +365,65 @@ def box_propagate_ransac(prev_pts: torch.Tensor, next_pts: torch.Tensor, status,
             inl.cpu().numpy()[:npts].copy())
 
 
+# cv::findHomography's methods (calib3d.hpp); LMEDS (4) and RHO (16) are not implemented
+LSQ, RANSAC = 0, 8
+
+
+class Homography:
+    """What find_homography returns, all on the device: H float64 [nsets, 3, 3]
+    (a view; the identity where valid is 0), mask uint8 per pair, and npoints
+    (-1 for a set of more than 4096 status != 0 pairs), ninliers, iters and
+    valid as int32 [nsets] views."""
+
+    def __init__(self, raw: torch.Tensor, mask: torch.Tensor, nsets: int):
+        self.raw, self.mask = raw, mask
+        f = raw.view(torch.float64).view(-1, C.sizeof(_lib.Homography) // 8)[:nsets]
+        i = raw.view(torch.int32).view(-1, C.sizeof(_lib.Homography) // 4)[:nsets]
+        self.H = f[:, :9].unflatten(1, (3, 3))
+        self.npoints, self.ninliers, self.iters, self.valid = i[:, 18], i[:, 19], i[:, 20], i[:, 21]
+
+
+def find_homography(src_pts: torch.Tensor, dst_pts: torch.Tensor, method: int = RANSAC,
+                    ransacReprojThreshold: float = 3.0, maxIters: int = 2000, confidence: float = 0.995,
+                    status: torch.Tensor | None = None, offsets: torch.Tensor | None = None, refine: bool = True,
+                    ctx: Context | None = None, stream=None) -> Homography:
+    """tbdk_find_homography: cv::findHomography(src, dst, method,
+    ransacReprojThreshold, mask, maxIters, confidence) per point set, on the
+    device.  src_pts / dst_pts: contiguous device float32 (N, 2); status: device
+    uint8 (N) or None (status == 0 pairs are dropped); offsets: device int32
+    (nsets + 1) or None for one set of all N pairs.  refine=False stops before
+    the reference's LM step.  Asynchronous: nothing is copied to the host and
+    the stream is not synchronised."""
+    for t in (src_pts, dst_pts) + tuple(t for t in (status, offsets) if t is not None):
+        if not t.is_cuda or not t.is_contiguous():
+            raise _lib.TbdkError("find_homography expects contiguous device tensors")
+    npts = src_pts.shape[0]
+    if (src_pts.dtype != torch.float32 or dst_pts.dtype != torch.float32 or src_pts.shape != (npts, 2)
+            or dst_pts.shape != (npts, 2)):
+        raise _lib.TbdkError("src_pts, dst_pts: float32 (N, 2)")
+    if status is not None and (status.dtype != torch.uint8 or status.numel() != npts):
+        raise _lib.TbdkError("status: uint8 (N)")
+    if offsets is None:
+        offsets = torch.tensor([0, npts], dtype=torch.int32, device=src_pts.device)
+    elif offsets.dtype != torch.int32 or offsets.numel() < 1:
+        raise _lib.TbdkError("offsets: int32 (nsets + 1)")
+    nsets = offsets.numel() - 1
+    ctx = ctx or Context.get(src_pts.device.index or 0)
+    par = _lib.HomographyParams()
+    _lib.check(ctx.lib.tbdk_homography_default_params(C.byref(par)), "tbdk_homography_default_params")
+    par.method, par.reproj_threshold, par.max_iters = int(method), float(ransacReprojThreshold), int(maxIters)
+    par.confidence, par.refine = float(confidence), 1 if refine else 0
+    raw = torch.zeros(max(1, nsets) * C.sizeof(_lib.Homography), dtype=torch.uint8, device=src_pts.device)
+    mask = torch.zeros(npts, dtype=torch.uint8, device=src_pts.device)
+    ptr = lambda t: C.c_void_p(t.data_ptr()) if t is not None and t.numel() else None  # noqa: E731
+    # an empty point tensor has no storage: any non-null pointer serves, nothing is read through it
+    pts = lambda t: C.c_void_p(t.data_ptr() if t.numel() else raw.data_ptr())  # noqa: E731
+    _lib.check(ctx.lib.tbdk_find_homography(ctx.handle, pts(src_pts), pts(dst_pts), ptr(status), ptr(offsets), nsets,
+                                            C.byref(par), ptr(raw), ptr(mask), _stream_ptr(stream)),
+               "tbdk_find_homography")
+    return Homography(raw, mask, nsets)
+
+
 # interpolation flags / border modes (reference values, imgproc.hpp / core/base.hpp)
 INTER_NEAREST, INTER_LINEAR, INTER_CUBIC, INTER_AREA, WARP_INVERSE_MAP = 0, 1, 2, 3, 16
 BORDER_CONSTANT, BORDER_REPLICATE, BORDER_REFLECT, BORDER_WRAP, BORDER_REFLECT_101, BORDER_TRANSPARENT = range(6)
@@ -497,14 +556,32 @@ def remap_flow(src: torch.Tensor, flow: torch.Tensor, sign: int = 1, interpolati
 
 def warp_perspective(src: torch.Tensor, M, dsize, flags: int = INTER_LINEAR, borderMode: int = BORDER_CONSTANT,
                      borderValue=0, dst: torch.Tensor | None = None, ctx: Context | None = None,
-                     stream=None) -> torch.Tensor:
+                     stream=None, valid: torch.Tensor | None = None) -> torch.Tensor:
     """cv::cuda::warpPerspective(src, dst, M, dsize, flags, borderMode, borderValue) for CV_8UC1..4 and
     CV_32FC1..4 with the CPU cv::warpPerspective's numerics (bit-exact).  M: 3x3 (host array-like, finite);
     dsize = (width, height).  Not equal to warp_affine for an affine M: the two round differently,
-    as the reference's two functions do."""
+    as the reference's two functions do.
+
+    M may also be a CUDA float64 tensor of nine elements (find_homography(...).H[i]): the matrix is
+    then read and inverted on the device when the kernel runs, with no host synchronisation, and the
+    result is byte-identical to the host-matrix call's.  `valid`: an optional device int32 element
+    (find_homography(...).valid[i]); where it reads 0, or M is not finite, dst is left as it was."""
     pix, cn = _warp_image(src, "warp_perspective")
     ctx = ctx or Context.get(src.device.index or 0)
     dst = _warp_dst(src, dst, int(dsize[1]), int(dsize[0]), "warp_perspective")
+    if isinstance(M, torch.Tensor) and M.is_cuda:
+        if M.dtype != torch.float64 or M.numel() != 9 or not M.is_contiguous():
+            raise _lib.TbdkError("warp_perspective: a device M is a contiguous float64 tensor of nine elements")
+        if valid is not None and (not valid.is_cuda or valid.dtype != torch.int32 or valid.numel() != 1):
+            raise _lib.TbdkError("warp_perspective: valid is one device int32")
+        _lib.check(ctx.lib.tbdk_warp_perspective_dev(ctx.handle, C.c_void_p(src.data_ptr()), pix, cn,
+                                                     *_image_args(src), C.c_void_p(dst.data_ptr()), *_image_args(dst),
+                                                     C.c_void_p(M.data_ptr()),
+                                                     C.c_void_p(valid.data_ptr()) if valid is not None else None,
+                                                     int(flags), int(borderMode), _border_value(borderValue),
+                                                     _stream_ptr(stream)),
+                   "tbdk_warp_perspective_dev")
+        return dst
     m = (C.c_double * 9)(*[float(v) for v in np.asarray(M, dtype=np.float64).reshape(9)])
     _lib.check(ctx.lib.tbdk_warp_perspective(ctx.handle, C.c_void_p(src.data_ptr()), pix, cn, *_image_args(src),
                                              C.c_void_p(dst.data_ptr()), *_image_args(dst), m, int(flags),

@@ -5,7 +5,8 @@ calcOpticalFlowFarneback, HOGDescriptor) on the cases of tests/_reference_cases.
 (goodFeaturesToTrack under a mask: tests/_gftt_mask_cases.py; the corner maps and
 goodFeaturesToTrack on CV_32F images: tests/_gftt_f32_cases.py; cornerSubPix:
 tests/_subpix_cases.py; goodFeaturesToTrack on whole frames:
-tests/_gftt_frame_cases.py; remap and warpPerspective: tests/_remap_cases.py)
+tests/_gftt_frame_cases.py; remap and warpPerspective: tests/_remap_cases.py;
+findHomography: tests/_homography_cases.py)
 into tests/golden/reference_<op>.npz, through tools/reference_driver.cpp (how to
 build it: tools/record_reference_cases.md).
 
@@ -45,6 +46,7 @@ import _subpix_cases as SC  # noqa: E402
 import _gftt_frame_cases as WC  # noqa: E402
 import _klt_tracker_oracle as KT  # noqa: E402
 import _remap_cases as PC  # noqa: E402
+import _homography_cases as HC  # noqa: E402
 
 LIMIT = 256 * 1024
 STATES = ("default", "noavx2")
@@ -52,7 +54,7 @@ STATES = ("default", "noavx2")
 MODELLED = {"pyramid": "both", "pyrlk": "both", "warpaffine": "both", "gftt": "noavx2", "gftt_mask": "noavx2",
             "cornermaps": "noavx2", "gftt_f32": "noavx2", "subpix": "both", "gftt_frame": "noavx2",
             "circle": "both", "remap": "both", "warpperspective": "both", "farneback": "noavx2",
-            "farneback_box": "noavx2", "hog": "default"}
+            "farneback_box": "noavx2", "hog": "default", "homography": "noavx2"}
 
 
 class Driver:
@@ -347,6 +349,27 @@ def rec_warpperspective(d):
     return cases, {}
 
 
+def rec_homography(d):
+    """findHomography on the status != 0 pairs (tests/_homography_cases.py): the mask bit-packed, the validity flag,
+    H as raw float64 (the identity where the result is empty); the point sets go in as extras"""
+    cases, extra = [], {}
+    assert len(HC.cases()) == HC.NCASES
+    for i in range(HC.NCASES):
+        src, dst, st, method, thr, iters, conf = HC.inputs(i)
+        extra[f"src_{i}"], extra[f"dst_{i}"] = src, dst
+        if st is not None:
+            extra[f"status_{i}"] = st
+        s, q = HC.compact(src, dst, st)
+        txt, rd = d.run("homography", dict(src=s, dst=q) if len(s) else {}, n=len(s), method=method, thr=float(thr),
+                        iters=iters, conf=float(conf))
+        valid = int(txt[0].split()[1])
+        h = rd("h", np.float64).reshape(3, 3) if valid else np.eye(3)
+        mask = rd("mask", np.uint8)
+        assert mask.size == len(s) and np.isin(mask, (0, 1)).all()
+        cases.append((dict(mask=np.packbits(mask), valid=np.array([valid, int(mask.sum())], np.int32)), dict(H=h)))
+    return cases, extra
+
+
 def rec_farneback(d, table=None):
     cases, meta = [], []
     for w, h, ps, pn, ws, flags, use_init in table or RC.FB_CASES:
@@ -448,12 +471,12 @@ RECORDERS = {"pyramid": rec_pyramid, "pyrlk": rec_pyrlk, "gftt": rec_gftt, "gftt
              "cornermaps": rec_cornermaps, "gftt_f32": rec_gftt_f32, "subpix": rec_subpix, "gftt_frame": rec_gftt_frame,
              "circle": rec_circle, "warpaffine": rec_warpaffine, "remap": rec_remap,
              "warpperspective": rec_warpperspective, "farneback": rec_farneback, "farneback_box": rec_farneback_box,
-             "hog": rec_hog}
+             "hog": rec_hog, "homography": rec_homography}
 # bytes up to which an output is stored whole (tests/_reference_cases.py: WHOLE_LIMIT).  The kernels are
 # compared with the box Farneback flows within a tolerance, so all six stay whole (about 7 KB under LIMIT)
 WHOLE = {"farneback": 20480, "farneback_box": 72800, "pyrlk": 1 << 20, "gftt": 1 << 20, "gftt_mask": 1 << 20,
          "hog": 16384, "subpix": 1 << 20, "gftt_frame": 1 << 20, "remap": PC.WHOLE_LIMIT,
-         "warpperspective": PC.WHOLE_LIMIT}
+         "warpperspective": PC.WHOLE_LIMIT, "homography": 1 << 20}
 # (gftt_f32: maps above RC.WHOLE_LIMIT as row CRCs; its corner lists are far below it)
 
 
@@ -492,6 +515,8 @@ def case_label(op, i):
         return PC.remap_label(i)
     if op == "warpperspective":
         return PC.persp_label(i)
+    if op == "homography":
+        return HC.label(i)
     if op == "circle":
         return "centre ({}, {}) radius {}".format(*KT.CIRCLE_CASES[i])
     if op == "cornermaps":
@@ -549,6 +574,10 @@ def main():
             else:
                 rec = {s: RECORDERS[op](drv[s]) for s in STATES}
             arrays, row = merge(op, rec, WHOLE.get(op, RC.WHOLE_LIMIT))
+            if op == "homography":  # the refined H is compared between the states by what it does to points: keep both
+                for i, ((_, f0), (_, f1)) in enumerate(zip(rec["default"][0], rec["noavx2"][0])):
+                    if f0["H"].tobytes() != f1["H"].tobytes():
+                        arrays[f"other_{i}_H"] = f0["H"]
             path = os.path.join(out_dir, f"reference_{op}.npz")
             save(path, arrays)
             size = os.path.getsize(path)

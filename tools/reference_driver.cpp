@@ -1,7 +1,7 @@
 // reference_driver.cpp — records the reference's CPU functions on raw files for
 // tests/golden/reference_<op>.npz (see tools/record_reference_cases.md).
-// Links against a scratch build of the reference's core, imgproc, video and
-// objdetect modules; nothing in the test suite builds or runs it.
+// Links against a scratch build of the reference's core, imgproc, video,
+// objdetect and calib3d modules; nothing in the test suite builds or runs it.
 //
 //   reference_driver <op> <out-prefix> key=value ...
 //
@@ -33,6 +33,10 @@
 //                                                  -> w (the image's type), minv (9 doubles): invert(M)
 //   circle  w= h= cx= cy= r=                       -> m (u8): circle(img, (cx, cy), r, Scalar(0), -1) on a 255-filled
 //                                                  CV_8UC1 image (no input image)
+//   homography src= dst= (f32 pairs, raw) n= method= thr= iters= conf=
+//                                                  -> h (9 doubles; nothing for an empty result), mask (n u8):
+//                                                  findHomography(src, dst, method, thr, mask, iters, conf); prints
+//                                                  "valid 0|1" (0 also where the reference throws, as it does for n = 0)
 #include <cmath>
 #include <cstdio>
 #include <cstdlib>
@@ -42,6 +46,7 @@
 #include <string>
 #include <vector>
 
+#include <opencv2/calib3d.hpp>
 #include <opencv2/core.hpp>
 #include <opencv2/imgproc.hpp>
 #include <opencv2/objdetect.hpp>
@@ -153,8 +158,36 @@ static int run_warps(const std::string& op, const std::string& out)
     return 0;
 }
 
+static int run_homography(const std::string& out)
+{
+    const int n = iarg("n");
+    std::vector<Point2f> p(n), q(n);
+    if (n) {
+        rd(arg("src"), p.data(), sizeof(Point2f) * n);
+        rd(arg("dst"), q.data(), sizeof(Point2f) * n);
+    }
+    Mat H, mask;
+    try {
+        H = findHomography(p, q, iarg("method"), darg("thr"), mask, iarg("iters"), darg("conf"));
+    } catch (const cv::Exception&) {
+        H.release();
+    }
+    const bool valid = !H.empty();
+    std::printf("valid %d\n", (int)valid);
+    std::vector<uchar> m(n, 0);
+    if (valid) {
+        if (H.type() != CV_64F || H.total() != 9 || (int)mask.total() != n || mask.type() != CV_8U)
+            throw std::runtime_error("findHomography: unexpected result type");
+        wr(out, "h", H);
+        if (n) std::memcpy(m.data(), mask.data, n);
+    }
+    wr(out, "mask", m.data(), n);
+    return 0;
+}
+
 static int run(const std::string& op, const std::string& out)
 {
+    if (op == "homography") return run_homography(out);
     const int w = iarg("w"), h = iarg("h"), cn = has("cn") ? iarg("cn") : 1;
     if (op == "remap" || op == "warpperspective") return run_warps(op, out);
     if (op == "circle") {
