@@ -771,6 +771,59 @@ int tbdk_find_homography(tbdk_ctx* ctx, const float* src_pts, const float* dst_p
                          const int32_t* offsets, int nsets, const tbdk_homography_params* params,
                          tbdk_homography* out, uint8_t* mask, void* stream);
 
+/* ---- estimateAffine2D / estimateAffinePartial2D ---------------------------------- */
+
+#define TBDK_AFFINE2D_FULL 0      /* estimateAffine2D, 3-point model */
+#define TBDK_AFFINE2D_PARTIAL 1   /* estimateAffinePartial2D, 2-point model */
+#define TBDK_AFFINE2D_RANSAC 8    /* cv::RANSAC */
+#define TBDK_AFFINE2D_LMEDS 4     /* cv::LMEDS */
+#define TBDK_AFFINE2D_MAX_PAIRS 4096  /* status != 0 pairs of one set the kernel holds */
+typedef struct tbdk_affine2d_params {
+    int32_t model;                 /* TBDK_AFFINE2D_FULL or _PARTIAL */
+    int32_t method;                /* TBDK_AFFINE2D_RANSAC or _LMEDS */
+    double  reproj_threshold;      /* RANSAC only; taken as given (<= 0 is not defaulted, as the reference) */
+    int32_t max_iters;             /* 1..10000, reference default 2000 */
+    double  confidence;            /* (0, 1), reference default 0.99 */
+    int32_t refine_iters;          /* 0..100 LM iterations, reference default 10; 0: stop before the LM step */
+} tbdk_affine2d_params;
+typedef struct tbdk_affine2d {
+    double  m[6];                  /* 2x3 row-major; [1 0 0; 0 1 0] when !valid */
+    int32_t npoints;               /* status != 0 pairs; -1 over the cap */
+    int32_t ninliers;              /* pairs the mask marks */
+    int32_t iters;                 /* RANSAC: iterations the reference's loop would have run; LMEDS: hypotheses
+                                    * evaluated; 0 when npoints equals the model's point count */
+    int32_t valid;                 /* the reference returned a non-empty matrix */
+} tbdk_affine2d;
+/* model FULL, method RANSAC, threshold 3, 2000 iterations, confidence 0.99, 10 refinement iterations */
+int tbdk_affine2d_default_params(tbdk_affine2d_params* p);
+
+/* Batched cv::estimateAffine2D / cv::estimateAffinePartial2D(from, to, inliers, method,
+ * ransacReprojThreshold, maxIters, confidence, refineIters) on point sets
+ * (calib3d/src/ptsetreg.cpp:821-980), one workgroup per set, nothing on the host: the
+ * reference's cv::RNG sequence seeded per set, getSubset's redraws and checkSubset, the
+ * closed-form 3-point or 2-point solver, the float error, RANSAC's strict "first best
+ * model wins" rule with RANSACUpdateNumIters or LMEDS's least median and its sigma, then
+ * the reference's LM refinement on the inliers in point order.
+ *   src_pts, dst_pts, status, offsets : as tbdk_find_homography
+ *   out[i]  : device; see tbdk_affine2d.  A set with fewer pairs than the model has
+ *             points (3 or 2), with no acceptable subset in iteration 0 or without
+ *             consensus has valid = 0 and the identity.  A set with exactly that many
+ *             pairs gets the solver's matrix (it may be NaN for degenerate pairs, as in
+ *             the reference).  More than TBDK_AFFINE2D_MAX_PAIRS status != 0 pairs: the
+ *             set is never truncated, npoints = -1, valid = 0
+ *   mask    : device u8 per pair or NULL: 1 for the inliers, 0 for outliers, status == 0
+ *             pairs and sets without a result; every byte is written once
+ * With refine_iters = 0, ninliers, iters, the mask and m are the reference's bit for bit
+ * (RANSACUpdateNumIters' log and pow aside); the refined m agrees with the
+ * reference's in what it does to the inlier points.  NaN or infinite points leave the
+ * call bounded; what m they give is unspecified.  Asynchronous on `stream`, no
+ * allocation, no host synchronisation; nsets == 0 is a no-op.  TBDK_EINVAL for max_iters
+ * outside 1..10000, confidence outside (0, 1), refine_iters outside 0..100, an unknown
+ * model or method, a non-finite threshold.  Timed as kernel "estimate_affine2d". */
+int tbdk_estimate_affine_2d(tbdk_ctx* ctx, const float* src_pts, const float* dst_pts, const uint8_t* status,
+                            const int32_t* offsets, int nsets, const tbdk_affine2d_params* params,
+                            tbdk_affine2d* out, uint8_t* mask, void* stream);
+
 /* ---- affine warp ------------------------------------------------------------ */
 
 /* interpolation flags / border modes: the reference's values
@@ -803,6 +856,18 @@ int tbdk_find_homography(tbdk_ctx* ctx, const float* src_pts, const float* dst_p
 int tbdk_warp_affine_u8(tbdk_ctx* ctx, const uint8_t* src, int src_width, int src_height, int src_pitch,
                         uint8_t* dst, int dst_width, int dst_height, int dst_pitch, const double* M,
                         int flags, int border, int border_value, void* stream);
+
+/* tbdk_warp_affine_u8 with the matrix in DEVICE memory, for a matrix an earlier call on the same
+ * stream produced (&out[i].m[0] of tbdk_estimate_affine_2d): no host round trip between the two.
+ *   M     : device pointer to 6 doubles, 8-byte aligned; read when the kernel runs.  It is inverted
+ *           on the device with tbdk_warp_affine_u8's arithmetic unless TBDK_WARP_INVERSE_MAP, so
+ *           for the same matrix the result is byte-identical to tbdk_warp_affine_u8
+ *   valid : device int32 or NULL (&out[i].valid).  Where it reads 0, or an entry of M is not
+ *           finite, dst is left untouched
+ * Timing name "warp_affine_dev". */
+int tbdk_warp_affine_u8_dev(tbdk_ctx* ctx, const uint8_t* src, int src_width, int src_height, int src_pitch,
+                            uint8_t* dst, int dst_width, int dst_height, int dst_pitch, const double* M,
+                            const int32_t* valid, int flags, int border, int border_value, void* stream);
 
 /* ---- remap, warpPerspective, warp by a dense flow --------------------------- */
 

@@ -735,6 +735,64 @@ inline void findHomography(Context& ctx, const float* src, const float* dst, con
           "tbdk_find_homography");
 }
 
+// cv::estimateAffine2D(from, to, inliers, method, ransacReprojThreshold, maxIters,
+// confidence, refineIters) (calib3d.hpp) on device point sets, batched and laid
+// out as findHomography above.  out (device, nsets entries) gets the 2x3 matrix
+// row-major, with valid = 0 and [1 0 0; 0 1 0] where the reference returns an
+// empty Mat; inliers (device u8 per pair, or nullptr) the mask.  method is RANSAC
+// (8) or LMEDS (4); the threshold is taken as given, as the reference takes it.
+// Nothing is copied to the host (tbdk_estimate_affine_2d).
+enum { LMEDS = TBDK_AFFINE2D_LMEDS };
+namespace detail {
+inline void estimate_affine(Context& ctx, int model, const float* from, const float* to, const uint8_t* status,
+                            const int32_t* offsets, int nsets, tbdk_affine2d* out, uint8_t* inliers, int method,
+                            double ransacReprojThreshold, int maxIters, double confidence, int refineIters,
+                            void* stream)
+{
+    tbdk_affine2d_params p;
+    check(tbdk_affine2d_default_params(&p), "tbdk_affine2d_default_params");
+    p.model = model;
+    p.method = method;
+    p.reproj_threshold = ransacReprojThreshold;
+    p.max_iters = maxIters;
+    p.confidence = confidence;
+    p.refine_iters = refineIters;
+    check(tbdk_estimate_affine_2d(ctx.get(), from, to, status, offsets, nsets, &p, out, inliers, stream),
+          "tbdk_estimate_affine_2d");
+}
+}  // namespace detail
+
+inline void estimateAffine2D(Context& ctx, const float* from, const float* to, const uint8_t* status,
+                             const int32_t* offsets, int nsets, tbdk_affine2d* out, uint8_t* inliers = nullptr,
+                             int method = RANSAC, double ransacReprojThreshold = 3.0, int maxIters = 2000,
+                             double confidence = 0.99, int refineIters = 10, void* stream = nullptr)
+{
+    detail::estimate_affine(ctx, TBDK_AFFINE2D_FULL, from, to, status, offsets, nsets, out, inliers, method,
+                            ransacReprojThreshold, maxIters, confidence, refineIters, stream);
+}
+
+// cv::estimateAffinePartial2D: the same with the 4-DOF model (rotation, uniform scale, translation)
+inline void estimateAffinePartial2D(Context& ctx, const float* from, const float* to, const uint8_t* status,
+                                    const int32_t* offsets, int nsets, tbdk_affine2d* out, uint8_t* inliers = nullptr,
+                                    int method = RANSAC, double ransacReprojThreshold = 3.0, int maxIters = 2000,
+                                    double confidence = 0.99, int refineIters = 10, void* stream = nullptr)
+{
+    detail::estimate_affine(ctx, TBDK_AFFINE2D_PARTIAL, from, to, status, offsets, nsets, out, inliers, method,
+                            ransacReprojThreshold, maxIters, confidence, refineIters, stream);
+}
+
+// warpAffine with M in DEVICE memory (six doubles, e.g. &A[i].m[0] of
+// estimateAffine2D, produced earlier on the same stream).  valid: an optional
+// device int32 (&A[i].valid); where it reads 0 dst is left untouched.
+inline void warpAffineDeviceMatrix(Context& ctx, const GpuImage& src, GpuImage& dst, const double* deviceM,
+                                   const int32_t* deviceValid = nullptr, int flags = TBDK_INTER_LINEAR,
+                                   int borderMode = TBDK_BORDER_CONSTANT, int borderValue = 0, void* stream = nullptr)
+{
+    check(tbdk_warp_affine_u8_dev(ctx.get(), src.data, src.width, src.height, src.pitch, dst.data, dst.width,
+                                  dst.height, dst.pitch, deviceM, deviceValid, flags, borderMode, borderValue, stream),
+          "tbdk_warp_affine_u8_dev");
+}
+
 // cv::cornerSubPix(image, corners, winSize, zeroZone, criteria) (imgproc.hpp;
 // imgproc/src/cornersubpix.cpp:44-156; the reference has no CUDA form) on the
 // device, with the CPU function's bits: corners is device memory, nrows x rowCap

@@ -143,6 +143,20 @@ class Homography(C.Structure):
                 ("valid", C.c_int32)]
 
 
+# include/tbdk.h: TBDK_AFFINE2D_*
+AFFINE2D_FULL, AFFINE2D_PARTIAL, AFFINE2D_RANSAC, AFFINE2D_LMEDS, AFFINE2D_MAX_PAIRS = 0, 1, 8, 4, 4096
+
+
+class Affine2DParams(C.Structure):
+    _fields_ = [("model", C.c_int32), ("method", C.c_int32), ("reproj_threshold", C.c_double),
+                ("max_iters", C.c_int32), ("confidence", C.c_double), ("refine_iters", C.c_int32)]
+
+
+class Affine2D(C.Structure):
+    _fields_ = [("m", C.c_double * 6), ("npoints", C.c_int32), ("ninliers", C.c_int32), ("iters", C.c_int32),
+                ("valid", C.c_int32)]
+
+
 class SubpixParams(C.Structure):
     _fields_ = [("win_w", C.c_int32), ("win_h", C.c_int32), ("zero_w", C.c_int32), ("zero_h", C.c_int32),
                 ("criteria", C.c_int32), ("max_count", C.c_int32), ("epsilon", C.c_double)]
@@ -315,6 +329,12 @@ SIGNATURES = {
     "tbdk_homography_default_params": (C.c_int, [C.POINTER(HomographyParams)]),
     "tbdk_find_homography": (C.c_int, [C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_int,
                                        C.POINTER(HomographyParams), C.c_void_p, C.c_void_p, C.c_void_p]),
+    "tbdk_affine2d_default_params": (C.c_int, [C.POINTER(Affine2DParams)]),
+    "tbdk_estimate_affine_2d": (C.c_int, [C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_int,
+                                          C.POINTER(Affine2DParams), C.c_void_p, C.c_void_p, C.c_void_p]),
+    "tbdk_warp_affine_u8_dev": (C.c_int, [C.c_void_p, C.c_void_p, C.c_int, C.c_int, C.c_int, C.c_void_p, C.c_int,
+                                          C.c_int, C.c_int, C.c_void_p, C.c_void_p, C.c_int, C.c_int, C.c_int,
+                                          C.c_void_p]),
     "tbdk_warp_affine_u8": (C.c_int, [C.c_void_p, C.c_void_p, C.c_int, C.c_int, C.c_int, C.c_void_p, C.c_int, C.c_int,
                                       C.c_int, C.POINTER(C.c_double), C.c_int, C.c_int, C.c_int, C.c_void_p]),
     # ctx, src, pix, cn, sw, sh, spitch, dst, dw, dh, dpitch, ...

@@ -1233,9 +1233,10 @@ int tbdk_box_propagate_ransac(tbdk_ctx* ctx, const float* prev_pts, const float*
     return map_err(e);
 }
 
-int tbdk_warp_affine_u8(tbdk_ctx* ctx, const uint8_t* src, int src_width, int src_height, int src_pitch,
-                        uint8_t* dst, int dst_width, int dst_height, int dst_pitch, const double* M,
-                        int flags, int border, int border_value, void* stream)
+// the argument checks tbdk_warp_affine_u8 and tbdk_warp_affine_u8_dev share; *inter is the kernel's mode
+static int warp_affine_check(tbdk_ctx* ctx, const uint8_t* src, int src_width, int src_height, int src_pitch,
+                             uint8_t* dst, int dst_width, int dst_height, int dst_pitch, const double* M, int flags,
+                             int border, int* inter_out)
 {
     if (!ctx || !src || !dst || !M) return TBDK_EINVAL;
     if (src_width <= 0 || src_height <= 0 || dst_width <= 0 || dst_height <= 0 || src_pitch < src_width ||
@@ -1253,6 +1254,37 @@ int tbdk_warp_affine_u8(tbdk_ctx* ctx, const uint8_t* src, int src_width, int sr
     const uint8_t* d0 = dst;
     const uint8_t* d1 = dst + (size_t)(dst_height - 1) * dst_pitch + dst_width;
     if (d0 < s1 && s0 < d1) return TBDK_EINVAL;
+    *inter_out = inter;
+    return TBDK_OK;
+}
+
+int tbdk_warp_affine_u8_dev(tbdk_ctx* ctx, const uint8_t* src, int src_width, int src_height, int src_pitch,
+                            uint8_t* dst, int dst_width, int dst_height, int dst_pitch, const double* M,
+                            const int32_t* valid, int flags, int border, int border_value, void* stream)
+{
+    int inter = 0;
+    const int st = warp_affine_check(ctx, src, src_width, src_height, src_pitch, dst, dst_width, dst_height, dst_pitch,
+                                     M, flags, border, &inter);
+    if (st != TBDK_OK) return st;
+    if ((reinterpret_cast<uintptr_t>(M) & 7) || (reinterpret_cast<uintptr_t>(valid) & 3)) return TBDK_EINVAL;
+    const int cval = border_value < 0 ? 0 : (border_value > 255 ? 255 : border_value);  // saturate_cast<uchar>
+    DeviceGuard g(ctx->device);
+    hipStream_t s = static_cast<hipStream_t>(stream);
+    int rec = timing_begin(ctx, "warp_affine_dev", s);
+    hipError_t e = launch_warp_affine_dev(src, src_width, src_height, src_pitch, dst, dst_width, dst_height, dst_pitch,
+                                          M, valid, (flags & TBDK_WARP_INVERSE_MAP) ? 1 : 0, inter, border, cval, s);
+    timing_end(ctx, rec, s);
+    return map_err(e);
+}
+
+int tbdk_warp_affine_u8(tbdk_ctx* ctx, const uint8_t* src, int src_width, int src_height, int src_pitch,
+                        uint8_t* dst, int dst_width, int dst_height, int dst_pitch, const double* M,
+                        int flags, int border, int border_value, void* stream)
+{
+    int inter = 0;
+    const int st = warp_affine_check(ctx, src, src_width, src_height, src_pitch, dst, dst_width, dst_height, dst_pitch,
+                                     M, flags, border, &inter);
+    if (st != TBDK_OK) return st;
     double minv[6];
     if (flags & TBDK_WARP_INVERSE_MAP) {
         for (int i = 0; i < 6; ++i) minv[i] = M[i];

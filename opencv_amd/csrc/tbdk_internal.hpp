@@ -323,6 +323,10 @@ hipError_t launch_box_propagate_ransac(const float* prev, const float* next, con
 void invert_affine(const double* M, double* out);
 hipError_t launch_warp_affine(const uint8_t* src, int sw, int sh, int spitch, uint8_t* dst, int dw, int dh, int dpitch,
                               const double* minv, int inter, int border, int cval, hipStream_t s);
+// M and valid in device memory; M is inverted on the device unless inverse_map
+hipError_t launch_warp_affine_dev(const uint8_t* src, int sw, int sh, int spitch, uint8_t* dst, int dw, int dh,
+                                  int dpitch, const double* M, const int32_t* valid, int inverse_map, int inter,
+                                  int border, int cval, hipStream_t s);
 
 // ---- image front end (frontend.hip): argument checks + launch, device already current ----
 void front_release(tbdk_ctx* ctx);

@@ -64,7 +64,7 @@ struct WarpArgs {
 };
 
 template <int INTER>
-__global__ __launch_bounds__(256) void warp_affine_kernel(WarpArgs a)
+__device__ __forceinline__ void warp_affine_rows(const WarpArgs a)
 {
     const int y = blockIdx.y;
     const int x0 = (blockIdx.x * blockDim.x + threadIdx.x) * 4;
@@ -195,10 +195,14 @@ __global__ __launch_bounds__(256) void warp_affine_kernel(WarpArgs a)
     }
 }
 
-}  // namespace
+template <int INTER>
+__global__ __launch_bounds__(256) void warp_affine_kernel(WarpArgs a)
+{
+    warp_affine_rows<INTER>(a);
+}
 
-// M inversion of cv::warpAffine (imgwarp.cpp:2606-2616), host double arithmetic
-void invert_affine(const double* M, double* out)
+// M inversion of cv::warpAffine (imgwarp.cpp:2606-2616), double arithmetic, the same on the host and the device
+__host__ __device__ inline void invert_affine_hd(const double* M, double* out)
 {
     double m[6];
     for (int i = 0; i < 6; ++i) m[i] = M[i];
@@ -216,8 +220,34 @@ void invert_affine(const double* M, double* out)
     for (int i = 0; i < 6; ++i) out[i] = m[i];
 }
 
-hipError_t launch_warp_affine(const uint8_t* src, int sw, int sh, int spitch, uint8_t* dst, int dw, int dh, int dpitch,
-                              const double* minv, int inter, int border, int cval, hipStream_t s)
+// warpAffine with the matrix in device memory (tbdk_warp_affine_u8_dev): every
+// thread reads the six doubles, inverts them unless the caller's matrix already
+// maps dst -> src (invert_affine's arithmetic) and runs the same sampling.  A
+// zero *valid or a non-finite entry leaves dst untouched.
+template <int INTER>
+__global__ __launch_bounds__(256) void warp_affine_dev_kernel(WarpArgs a, const double* __restrict__ M,
+                                                              const int32_t* __restrict__ valid, int inverse_map)
+{
+    if (valid && *valid == 0) return;
+    double m[6];
+    bool finite = true;
+#pragma unroll
+    for (int i = 0; i < 6; ++i) {
+        m[i] = M[i];
+        finite = finite && isfinite(m[i]);
+    }
+    if (!finite) return;
+    if (inverse_map) {
+#pragma unroll
+        for (int i = 0; i < 6; ++i) a.m[i] = m[i];
+    } else {
+        invert_affine_hd(m, a.m);
+    }
+    warp_affine_rows<INTER>(a);
+}
+
+WarpArgs warp_args(const uint8_t* src, int sw, int sh, int spitch, uint8_t* dst, int dw, int dh, int dpitch, int inter,
+                   int border, int cval)
 {
     WarpArgs a;
     a.src = src;
@@ -228,10 +258,34 @@ hipError_t launch_warp_affine(const uint8_t* src, int sw, int sh, int spitch, ui
     a.dw = dw;
     a.dh = dh;
     a.dpitch = dpitch;
-    for (int i = 0; i < 6; ++i) a.m[i] = minv[i];
+    for (int i = 0; i < 6; ++i) a.m[i] = 0;
     a.inter = inter;
     a.border = border;
     a.cval = cval;
+    return a;
+}
+
+}  // namespace
+
+void invert_affine(const double* M, double* out) { invert_affine_hd(M, out); }
+
+hipError_t launch_warp_affine_dev(const uint8_t* src, int sw, int sh, int spitch, uint8_t* dst, int dw, int dh,
+                                  int dpitch, const double* M, const int32_t* valid, int inverse_map, int inter,
+                                  int border, int cval, hipStream_t s)
+{
+    const WarpArgs a = warp_args(src, sw, sh, spitch, dst, dw, dh, dpitch, inter, border, cval);
+    const dim3 grid((dw + 4 * 256 - 1) / (4 * 256), dh), block(256);
+    if (inter == 0) hipLaunchKernelGGL(warp_affine_dev_kernel<0>, grid, block, 0, s, a, M, valid, inverse_map);
+    else if (inter == 2) hipLaunchKernelGGL(warp_affine_dev_kernel<2>, grid, block, 0, s, a, M, valid, inverse_map);
+    else hipLaunchKernelGGL(warp_affine_dev_kernel<1>, grid, block, 0, s, a, M, valid, inverse_map);
+    return hipGetLastError();
+}
+
+hipError_t launch_warp_affine(const uint8_t* src, int sw, int sh, int spitch, uint8_t* dst, int dw, int dh, int dpitch,
+                              const double* minv, int inter, int border, int cval, hipStream_t s)
+{
+    WarpArgs a = warp_args(src, sw, sh, spitch, dst, dw, dh, dpitch, inter, border, cval);
+    for (int i = 0; i < 6; ++i) a.m[i] = minv[i];
     const dim3 grid((dw + 4 * 256 - 1) / (4 * 256), dh), block(256);
     if (inter == 0) hipLaunchKernelGGL(warp_affine_kernel<0>, grid, block, 0, s, a);
     else if (inter == 2) hipLaunchKernelGGL(warp_affine_kernel<2>, grid, block, 0, s, a);

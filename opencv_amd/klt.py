@@ -424,6 +424,81 @@ def find_homography(src_pts: torch.Tensor, dst_pts: torch.Tensor, method: int = 
     return Homography(raw, mask, nsets)
 
 
+# cv::estimateAffine2D's robust methods (calib3d.hpp); RANSAC is 8 as above
+LMEDS = 4
+
+
+class Affine2D:
+    """What estimate_affine_2d / estimate_affine_partial_2d return, all on the
+    device: M float64 [nsets, 2, 3] (a view; [1 0 0; 0 1 0] where valid is 0),
+    mask uint8 per pair, and npoints (-1 for a set of more than 4096
+    status != 0 pairs), ninliers, iters and valid as int32 [nsets] views."""
+
+    def __init__(self, raw: torch.Tensor, mask: torch.Tensor, nsets: int):
+        self.raw, self.mask = raw, mask
+        f = raw.view(torch.float64).view(-1, C.sizeof(_lib.Affine2D) // 8)[:nsets]
+        i = raw.view(torch.int32).view(-1, C.sizeof(_lib.Affine2D) // 4)[:nsets]
+        self.M = f[:, :6].unflatten(1, (2, 3))
+        self.npoints, self.ninliers, self.iters, self.valid = i[:, 12], i[:, 13], i[:, 14], i[:, 15]
+
+
+def _estimate_affine(model: int, what: str, src_pts, dst_pts, method, thr, max_iters, confidence, refine_iters,
+                     status, offsets, ctx, stream) -> Affine2D:
+    for t in (src_pts, dst_pts) + tuple(t for t in (status, offsets) if t is not None):
+        if not t.is_cuda or not t.is_contiguous():
+            raise _lib.TbdkError(f"{what} expects contiguous device tensors")
+    npts = src_pts.shape[0]
+    if (src_pts.dtype != torch.float32 or dst_pts.dtype != torch.float32 or src_pts.shape != (npts, 2)
+            or dst_pts.shape != (npts, 2)):
+        raise _lib.TbdkError("from_pts, to_pts: float32 (N, 2)")
+    if status is not None and (status.dtype != torch.uint8 or status.numel() != npts):
+        raise _lib.TbdkError("status: uint8 (N)")
+    if offsets is None:
+        offsets = torch.tensor([0, npts], dtype=torch.int32, device=src_pts.device)
+    elif offsets.dtype != torch.int32 or offsets.numel() < 1:
+        raise _lib.TbdkError("offsets: int32 (nsets + 1)")
+    nsets = offsets.numel() - 1
+    ctx = ctx or Context.get(src_pts.device.index or 0)
+    par = _lib.Affine2DParams()
+    _lib.check(ctx.lib.tbdk_affine2d_default_params(C.byref(par)), "tbdk_affine2d_default_params")
+    par.model, par.method, par.reproj_threshold = int(model), int(method), float(thr)
+    par.max_iters, par.confidence, par.refine_iters = int(max_iters), float(confidence), int(refine_iters)
+    raw = torch.zeros(max(1, nsets) * C.sizeof(_lib.Affine2D), dtype=torch.uint8, device=src_pts.device)
+    mask = torch.zeros(npts, dtype=torch.uint8, device=src_pts.device)
+    ptr = lambda t: C.c_void_p(t.data_ptr()) if t is not None and t.numel() else None  # noqa: E731
+    # an empty point tensor has no storage: any non-null pointer serves, nothing is read through it
+    pts = lambda t: C.c_void_p(t.data_ptr() if t.numel() else raw.data_ptr())  # noqa: E731
+    _lib.check(ctx.lib.tbdk_estimate_affine_2d(ctx.handle, pts(src_pts), pts(dst_pts), ptr(status), ptr(offsets),
+                                               nsets, C.byref(par), ptr(raw), ptr(mask), _stream_ptr(stream)),
+               "tbdk_estimate_affine_2d")
+    return Affine2D(raw, mask, nsets)
+
+
+def estimate_affine_2d(from_pts: torch.Tensor, to_pts: torch.Tensor, method: int = RANSAC,
+                       ransacReprojThreshold: float = 3.0, maxIters: int = 2000, confidence: float = 0.99,
+                       refineIters: int = 10, status: torch.Tensor | None = None,
+                       offsets: torch.Tensor | None = None, ctx: Context | None = None, stream=None) -> Affine2D:
+    """tbdk_estimate_affine_2d with the 3-point model: cv::estimateAffine2D(from, to, inliers, method,
+    ransacReprojThreshold, maxIters, confidence, refineIters) per point set, on the device (method RANSAC
+    or LMEDS).  from_pts / to_pts: contiguous device float32 (N, 2); status: device uint8 (N) or None
+    (status == 0 pairs are dropped); offsets: device int32 (nsets + 1) or None for one set of all N pairs.
+    refineIters=0 stops before the reference's LM step.  Asynchronous: nothing is copied to the host and
+    the stream is not synchronised."""
+    return _estimate_affine(_lib.AFFINE2D_FULL, "estimate_affine_2d", from_pts, to_pts, method,
+                            ransacReprojThreshold, maxIters, confidence, refineIters, status, offsets, ctx, stream)
+
+
+def estimate_affine_partial_2d(from_pts: torch.Tensor, to_pts: torch.Tensor, method: int = RANSAC,
+                               ransacReprojThreshold: float = 3.0, maxIters: int = 2000, confidence: float = 0.99,
+                               refineIters: int = 10, status: torch.Tensor | None = None,
+                               offsets: torch.Tensor | None = None, ctx: Context | None = None,
+                               stream=None) -> Affine2D:
+    """estimate_affine_2d with the 2-point model (rotation, uniform scale, translation):
+    cv::estimateAffinePartial2D."""
+    return _estimate_affine(_lib.AFFINE2D_PARTIAL, "estimate_affine_partial_2d", from_pts, to_pts, method,
+                            ransacReprojThreshold, maxIters, confidence, refineIters, status, offsets, ctx, stream)
+
+
 # interpolation flags / border modes (reference values, imgproc.hpp / core/base.hpp)
 INTER_NEAREST, INTER_LINEAR, INTER_CUBIC, INTER_AREA, WARP_INVERSE_MAP = 0, 1, 2, 3, 16
 BORDER_CONSTANT, BORDER_REPLICATE, BORDER_REFLECT, BORDER_WRAP, BORDER_REFLECT_101, BORDER_TRANSPARENT = range(6)
@@ -431,11 +506,16 @@ BORDER_CONSTANT, BORDER_REPLICATE, BORDER_REFLECT, BORDER_WRAP, BORDER_REFLECT_1
 
 def warp_affine(src: torch.Tensor, M, dsize, flags: int = INTER_LINEAR, borderMode: int = BORDER_CONSTANT,
                 borderValue: int = 0, dst: torch.Tensor | None = None, ctx: Context | None = None,
-                stream=None) -> torch.Tensor:
+                stream=None, valid: torch.Tensor | None = None) -> torch.Tensor:
     """cv::cuda::warpAffine(src, dst, M, dsize, flags, borderMode, borderValue) for CV_8UC1
     (cudawarping.hpp:126) with the CPU cv::warpAffine's fixed-point numerics (bit-exact).
     M: 2x3 (host array-like); dsize = (width, height).  `dst` may be passed to keep its
-    contents where BORDER_TRANSPARENT leaves pixels untouched."""
+    contents where BORDER_TRANSPARENT leaves pixels untouched.
+
+    M may also be a CUDA float64 tensor of six elements (estimate_affine_2d(...).M[i]): the matrix is
+    then read and inverted on the device when the kernel runs, with no host synchronisation, and the
+    result is byte-identical to the host-matrix call's.  `valid`: an optional device int32 element
+    (estimate_affine_2d(...).valid[i]); where it reads 0, or M is not finite, dst is left as it was."""
     if src.dtype != torch.uint8 or src.dim() != 2 or not src.is_cuda or src.stride(1) != 1:
         raise _lib.TbdkError("warp_affine expects a 2-D uint8 device tensor")
     ctx = ctx or Context.get(src.device.index or 0)
@@ -444,8 +524,21 @@ def warp_affine(src: torch.Tensor, M, dsize, flags: int = INTER_LINEAR, borderMo
         dst = torch.zeros((dh, dw), dtype=torch.uint8, device=src.device)
     elif dst.shape != (dh, dw) or dst.dtype != torch.uint8 or dst.stride(1) != 1:
         raise _lib.TbdkError("dst must be a (height, width) uint8 device tensor")
-    m = (C.c_double * 6)(*[float(v) for v in np.asarray(M, dtype=np.float64).reshape(6)])
     h, w = src.shape
+    if isinstance(M, torch.Tensor) and M.is_cuda:
+        if M.dtype != torch.float64 or M.numel() != 6 or not M.is_contiguous():
+            raise _lib.TbdkError("warp_affine: a device M is a contiguous float64 tensor of six elements")
+        if valid is not None and (not valid.is_cuda or valid.dtype != torch.int32 or valid.numel() != 1):
+            raise _lib.TbdkError("warp_affine: valid is one device int32")
+        _lib.check(ctx.lib.tbdk_warp_affine_u8_dev(ctx.handle, C.c_void_p(src.data_ptr()), w, h, src.stride(0),
+                                                   C.c_void_p(dst.data_ptr()), dw, dh, dst.stride(0),
+                                                   C.c_void_p(M.data_ptr()),
+                                                   C.c_void_p(valid.data_ptr()) if valid is not None else None,
+                                                   int(flags), int(borderMode), int(borderValue),
+                                                   _stream_ptr(stream)),
+                   "tbdk_warp_affine_u8_dev")
+        return dst
+    m = (C.c_double * 6)(*[float(v) for v in np.asarray(M, dtype=np.float64).reshape(6)])
     _lib.check(ctx.lib.tbdk_warp_affine_u8(ctx.handle, C.c_void_p(src.data_ptr()), w, h, src.stride(0),
                                            C.c_void_p(dst.data_ptr()), dw, dh, dst.stride(0), m, int(flags),
                                            int(borderMode), int(borderValue), _stream_ptr(stream)),

@@ -6,7 +6,8 @@ calcOpticalFlowFarneback, HOGDescriptor) on the cases of tests/_reference_cases.
 goodFeaturesToTrack on CV_32F images: tests/_gftt_f32_cases.py; cornerSubPix:
 tests/_subpix_cases.py; goodFeaturesToTrack on whole frames:
 tests/_gftt_frame_cases.py; remap and warpPerspective: tests/_remap_cases.py;
-findHomography: tests/_homography_cases.py)
+findHomography: tests/_homography_cases.py; estimateAffine2D and
+estimateAffinePartial2D: tests/_affine2d_cases.py)
 into tests/golden/reference_<op>.npz, through tools/reference_driver.cpp (how to
 build it: tools/record_reference_cases.md).
 
@@ -47,6 +48,7 @@ import _gftt_frame_cases as WC  # noqa: E402
 import _klt_tracker_oracle as KT  # noqa: E402
 import _remap_cases as PC  # noqa: E402
 import _homography_cases as HC  # noqa: E402
+import _affine2d_cases as AC  # noqa: E402
 
 LIMIT = 256 * 1024
 STATES = ("default", "noavx2")
@@ -54,7 +56,7 @@ STATES = ("default", "noavx2")
 MODELLED = {"pyramid": "both", "pyrlk": "both", "warpaffine": "both", "gftt": "noavx2", "gftt_mask": "noavx2",
             "cornermaps": "noavx2", "gftt_f32": "noavx2", "subpix": "both", "gftt_frame": "noavx2",
             "circle": "both", "remap": "both", "warpperspective": "both", "farneback": "noavx2",
-            "farneback_box": "noavx2", "hog": "default", "homography": "noavx2"}
+            "farneback_box": "noavx2", "hog": "default", "homography": "noavx2", "affine2d": "noavx2"}
 
 
 class Driver:
@@ -370,6 +372,33 @@ def rec_homography(d):
     return cases, extra
 
 
+def rec_affine2d(d):
+    """estimateAffine2D / estimateAffinePartial2D on the status != 0 pairs (tests/_affine2d_cases.py), with
+    refineIters 0 and 10: the mask bit-packed, the validity flag, M as raw float64 (the identity where the result is
+    empty); the distinct point sets go in as extras"""
+    cases, extra = [], {}
+    assert len(AC.cases()) == AC.NCASES
+    ids, keys = AC.set_ids()
+    for k, key in enumerate(keys):
+        extra[f"set_{k}_src"], extra[f"set_{k}_dst"] = AC.points(*key)
+    for i in range(AC.NCASES):
+        src, dst, st, model, method, thr, iters, conf = AC.inputs(i)
+        assert np.array_equal(src, extra[f"set_{ids[i]}_src"]) and np.array_equal(dst, extra[f"set_{ids[i]}_dst"])
+        s, q = AC.compact(src, dst, st)
+        ints, floats = {}, {}
+        for refine in (0, 10):
+            txt, rd = d.run("affine2d", dict(src=s, dst=q) if len(s) else {}, n=len(s), model=model, method=method,
+                            thr=float(thr), iters=iters, conf=float(conf), refine=refine)
+            valid = int(txt[0].split()[1])
+            mask = rd("mask", np.uint8)
+            assert mask.size == len(s) and np.isin(mask, (0, 1)).all()
+            ints[f"r{refine}_mask"] = np.packbits(mask)
+            ints[f"r{refine}_valid"] = np.array([valid, int(mask.sum())], np.int32)
+            floats[f"r{refine}_M"] = rd("m", np.float64).reshape(2, 3) if valid else np.eye(2, 3)
+        cases.append((ints, floats))
+    return cases, extra
+
+
 def rec_farneback(d, table=None):
     cases, meta = [], []
     for w, h, ps, pn, ws, flags, use_init in table or RC.FB_CASES:
@@ -471,12 +500,12 @@ RECORDERS = {"pyramid": rec_pyramid, "pyrlk": rec_pyrlk, "gftt": rec_gftt, "gftt
              "cornermaps": rec_cornermaps, "gftt_f32": rec_gftt_f32, "subpix": rec_subpix, "gftt_frame": rec_gftt_frame,
              "circle": rec_circle, "warpaffine": rec_warpaffine, "remap": rec_remap,
              "warpperspective": rec_warpperspective, "farneback": rec_farneback, "farneback_box": rec_farneback_box,
-             "hog": rec_hog, "homography": rec_homography}
+             "hog": rec_hog, "homography": rec_homography, "affine2d": rec_affine2d}
 # bytes up to which an output is stored whole (tests/_reference_cases.py: WHOLE_LIMIT).  The kernels are
 # compared with the box Farneback flows within a tolerance, so all six stay whole (about 7 KB under LIMIT)
 WHOLE = {"farneback": 20480, "farneback_box": 72800, "pyrlk": 1 << 20, "gftt": 1 << 20, "gftt_mask": 1 << 20,
          "hog": 16384, "subpix": 1 << 20, "gftt_frame": 1 << 20, "remap": PC.WHOLE_LIMIT,
-         "warpperspective": PC.WHOLE_LIMIT, "homography": 1 << 20}
+         "warpperspective": PC.WHOLE_LIMIT, "homography": 1 << 20, "affine2d": 1 << 20}
 # (gftt_f32: maps above RC.WHOLE_LIMIT as row CRCs; its corner lists are far below it)
 
 
@@ -517,6 +546,8 @@ def case_label(op, i):
         return PC.persp_label(i)
     if op == "homography":
         return HC.label(i)
+    if op == "affine2d":
+        return AC.label(i)
     if op == "circle":
         return "centre ({}, {}) radius {}".format(*KT.CIRCLE_CASES[i])
     if op == "cornermaps":
@@ -578,6 +609,11 @@ def main():
                 for i, ((_, f0), (_, f1)) in enumerate(zip(rec["default"][0], rec["noavx2"][0])):
                     if f0["H"].tobytes() != f1["H"].tobytes():
                         arrays[f"other_{i}_H"] = f0["H"]
+            if op == "affine2d" and row[0] != "both":  # both states' M wherever they differ
+                for i, ((_, f0), (_, f1)) in enumerate(zip(rec["default"][0], rec["noavx2"][0])):
+                    for k in f0:
+                        if f0[k].tobytes() != f1[k].tobytes():
+                            arrays[f"other_{i}_{k}"] = f0[k]
             path = os.path.join(out_dir, f"reference_{op}.npz")
             save(path, arrays)
             size = os.path.getsize(path)

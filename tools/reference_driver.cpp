@@ -37,6 +37,10 @@
 //                                                  -> h (9 doubles; nothing for an empty result), mask (n u8):
 //                                                  findHomography(src, dst, method, thr, mask, iters, conf); prints
 //                                                  "valid 0|1" (0 also where the reference throws, as it does for n = 0)
+//   affine2d src= dst= (f32 pairs, raw) n= model=0|1 method= thr= iters= conf= refine=
+//                                                  -> m (6 doubles; nothing for an empty result), mask (n u8):
+//                                                  estimateAffine2D (model 0) or estimateAffinePartial2D (model 1)
+//                                                  (src, dst, mask, method, thr, iters, conf, refine); prints "valid 0|1"
 #include <cmath>
 #include <cstdio>
 #include <cstdlib>
@@ -185,9 +189,42 @@ static int run_homography(const std::string& out)
     return 0;
 }
 
+static int run_affine2d(const std::string& out)
+{
+    const int n = iarg("n");
+    std::vector<Point2f> p(n), q(n);
+    if (n) {
+        rd(arg("src"), p.data(), sizeof(Point2f) * n);
+        rd(arg("dst"), q.data(), sizeof(Point2f) * n);
+    }
+    Mat M, mask;
+    try {
+        if (iarg("model") == 0)
+            M = estimateAffine2D(p, q, mask, iarg("method"), darg("thr"), (size_t)iarg("iters"), darg("conf"),
+                                 (size_t)iarg("refine"));
+        else
+            M = estimateAffinePartial2D(p, q, mask, iarg("method"), darg("thr"), (size_t)iarg("iters"), darg("conf"),
+                                        (size_t)iarg("refine"));
+    } catch (const cv::Exception&) {
+        M.release();
+    }
+    const bool valid = !M.empty();
+    std::printf("valid %d\n", (int)valid);
+    std::vector<uchar> m(n, 0);
+    if (valid) {
+        if (M.type() != CV_64F || M.total() != 6 || (int)mask.total() != n || mask.type() != CV_8U)
+            throw std::runtime_error("estimateAffine2D: unexpected result type");
+        wr(out, "m", M);
+        if (n) std::memcpy(m.data(), mask.data, n);
+    }
+    wr(out, "mask", m.data(), n);
+    return 0;
+}
+
 static int run(const std::string& op, const std::string& out)
 {
     if (op == "homography") return run_homography(out);
+    if (op == "affine2d") return run_affine2d(out);
     const int w = iarg("w"), h = iarg("h"), cn = has("cn") ? iarg("cn") : 1;
     if (op == "remap" || op == "warpperspective") return run_warps(op, out);
     if (op == "circle") {
