@@ -1560,6 +1560,68 @@ int tbdk_klt_tracker_device_state(tbdk_klt_tracker* tr, const int32_t** count, c
 int tbdk_mask_circles_u8(tbdk_ctx* ctx, uint8_t* mask, int width, int height, int pitch, const float* pts,
                          const int32_t* count_dev, int n, int radius, int value, void* stream);
 
+/* ---- background subtraction ------------------------------------------------ */
+
+/* cv::BackgroundSubtractorMOG2 (video/src/bgfg_gaussmix2.cpp) with its model resident on the
+ * device: per pixel up to `nmixtures` Gaussian modes (weight, variance, mean per channel) and
+ * the count of modes in use.  One kernel per frame classifies every pixel and updates its
+ * model in place, with the reference's scalar float arithmetic operation for operation: the
+ * mask, the background image and the model are the reference's bit for bit.
+ * Frames: TBDK_DEPTH_8U or TBDK_DEPTH_32F, 1 or 3 channels, pitched, any alignment (32F: pointer
+ * and pitch multiples of 4). */
+typedef struct tbdk_mog2 tbdk_mog2;
+
+typedef struct tbdk_mog2_config {
+    int32_t width, height, depth, channels;  /* fixed at creation */
+    int32_t history;                /* 500 */
+    int32_t nmixtures;              /* 5; 1..8, fixed at creation */
+    int32_t detect_shadows;         /* 1 */
+    int32_t shadow_value;           /* 127; 0..255 */
+    double  var_threshold;          /* 16 (Tb; the reference holds it as a double) */
+    float   var_threshold_gen;      /* 9 (Tg) */
+    float   var_init, var_min, var_max;  /* 15, 4, 75; the smaller of var_min / var_max is the lower clamp */
+    float   background_ratio;       /* 0.9 (TB) */
+    float   complexity_reduction;   /* 0.05 (CT) */
+    float   shadow_threshold;       /* 0.5 (tau) */
+    int32_t reserved;               /* 0 */
+} tbdk_mog2_config;
+
+/* the reference's defaults for a frame of this size and type */
+int tbdk_mog2_config_default(int width, int height, int depth, int channels, tbdk_mog2_config* cfg);
+/* Allocates the model (nothing is allocated afterwards).  TBDK_EINVAL: a depth other than 8U / 32F,
+ * channels other than 1 / 3, nmixtures outside 1..8, width or height outside 1..65535, history < 1,
+ * shadow_value outside 0..255. */
+int tbdk_mog2_create(tbdk_ctx* ctx, const tbdk_mog2_config* cfg, tbdk_mog2** out);
+int tbdk_mog2_destroy(tbdk_mog2* m);
+/* The next apply starts from an empty model (frames() becomes 0).  No device work. */
+int tbdk_mog2_reset(tbdk_mog2* m);
+/* The reference's setters, all at once: takes every field of cfg but the fixed ones, which must
+ * equal the object's (TBDK_EINVAL otherwise, nothing changed).  Holds from the next apply on. */
+int tbdk_mog2_set_params(tbdk_mog2* m, const tbdk_mog2_config* cfg);
+/* apply(frame, fgmask, learningRate): fgmask (device, 8-bit, width x height, mask_pitch bytes a
+ * row) gets 0 (background), shadow_value (shadow) or 255 per pixel, and the model is updated.
+ * The schedule is the reference's, kept on the host: the model is cleared (on the stream) on the
+ * first call, after tbdk_mog2_reset and when learning_rate >= 1; the frame count is then
+ * incremented, and the rate is learning_rate if it is >= 0 and this is not the first frame, else
+ * 1 / min(2 * frames, history).  Asynchronous on `stream`, no allocation, no host
+ * synchronisation; calls on one object are ordered by the caller's stream(s).  TBDK_EINVAL
+ * (nothing enqueued, nothing changed): a null pointer, a pitch below a row, a 32F frame whose
+ * pointer or pitch is no multiple of 4, a learning rate that is NaN.  Timed as "mog2_apply". */
+int tbdk_mog2_apply(tbdk_mog2* m, const void* frame, int pitch, uint8_t* fgmask, int mask_pitch,
+                    double learning_rate, void* stream);
+/* getBackgroundImage: the weighted mean of each pixel's background modes, in the frame's type
+ * (8-bit: rounded half to even and clamped), 0 where a pixel has no mode.  img: device, pitch in
+ * bytes (32F: as for the frame).  Timed as "mog2_background". */
+int tbdk_mog2_get_background(tbdk_mog2* m, void* img, int pitch, void* stream);
+/* The model in the reference's layout, for tests and checkpoints (device pointers, any may be
+ * NULL): weight[h][w][K], variance[h][w][K], mean[h][w][K][channels] (float32) and
+ * modes_used[h][w] (uint8), K = nmixtures, all tight.  Modes at and above modes_used hold
+ * whatever they last held, as in the reference.  Timed as "mog2_model". */
+int tbdk_mog2_get_model(tbdk_mog2* m, float* weight, float* variance, float* mean, uint8_t* modes_used,
+                        void* stream);
+/* frames applied since the model was last cleared */
+int tbdk_mog2_frames(tbdk_mog2* m, int* nframes);
+
 /* ---- synthetic sequences (bench / test input) ----------------------------- */
 
 /* Renders frames [t0, t0+nframes) of the deterministic synthetic sequence of

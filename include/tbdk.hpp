@@ -1017,6 +1017,116 @@ private:
     int track_len_ = 0;
 };
 
+// cv::BackgroundSubtractorMOG2 / cv::cuda::BackgroundSubtractorMOG2 (video/background_segm.hpp:90-219,
+// cudabgsegm.hpp) over tbdk_mog2: the model stays on the device, apply() only enqueues work.  The model is
+// allocated by the first apply, from the frame's size and type, which may not change afterwards; so may
+// nmixtures not.  Masks, background images and the model are the CPU reference's bit for bit.
+class BackgroundSubtractorMOG2 {
+public:
+    BackgroundSubtractorMOG2(Context& ctx, int history = 500, double varThreshold = 16, bool detectShadows = true)
+        : ctx_(&ctx)
+    {
+        check(tbdk_mog2_config_default(0, 0, DEPTH_8U, 1, &cfg_), "tbdk_mog2_config_default");
+        // the reference's constructor keeps its defaults for non-positive arguments (bgfg_gaussmix2.cpp:157-158)
+        if (history > 0) cfg_.history = history;
+        if (varThreshold > 0) cfg_.var_threshold = varThreshold;
+        cfg_.detect_shadows = detectShadows ? 1 : 0;
+    }
+    ~BackgroundSubtractorMOG2()
+    {
+        if (h_) tbdk_mog2_destroy(h_);
+    }
+    BackgroundSubtractorMOG2(const BackgroundSubtractorMOG2&) = delete;
+    BackgroundSubtractorMOG2& operator=(const BackgroundSubtractorMOG2&) = delete;
+
+    // image: 8U or 32F, 1 or 3 channels; fgmask: 8-bit, the image's size
+    void apply(const GpuMatView& image, const GpuImage& fgmask, double learningRate = -1, void* stream = nullptr)
+    {
+        if (!h_) {
+            cfg_.width = image.width, cfg_.height = image.height, cfg_.depth = image.depth, cfg_.channels = image.cn;
+            check(tbdk_mog2_create(ctx_->get(), &cfg_, &h_), "tbdk_mog2_create");
+        }
+        if (image.width != cfg_.width || image.height != cfg_.height || image.depth != cfg_.depth ||
+            image.cn != cfg_.channels || fgmask.width != cfg_.width || fgmask.height != cfg_.height)
+            throw Error(TBDK_EINVAL, "BackgroundSubtractorMOG2::apply: the frame's size and type may not change");
+        check(tbdk_mog2_apply(h_, image.data, image.pitch, fgmask.data, fgmask.pitch, learningRate, stream),
+              "tbdk_mog2_apply");
+    }
+    void getBackgroundImage(const GpuMatView& backgroundImage, void* stream = nullptr)
+    {
+        if (!h_ || backgroundImage.width != cfg_.width || backgroundImage.height != cfg_.height ||
+            backgroundImage.depth != cfg_.depth || backgroundImage.cn != cfg_.channels)
+            throw Error(TBDK_EINVAL, "BackgroundSubtractorMOG2::getBackgroundImage: an image of the frames' size and type");
+        check(tbdk_mog2_get_background(h_, backgroundImage.data, backgroundImage.pitch, stream),
+              "tbdk_mog2_get_background");
+    }
+    void reset()
+    {
+        if (h_) check(tbdk_mog2_reset(h_), "tbdk_mog2_reset");
+    }
+    int frames() const
+    {
+        int n = 0;
+        if (h_) check(tbdk_mog2_frames(h_, &n), "tbdk_mog2_frames");
+        return n;
+    }
+
+    int getHistory() const { return cfg_.history; }
+    void setHistory(int v) { set(&tbdk_mog2_config::history, v); }
+    int getNMixtures() const { return cfg_.nmixtures; }
+    void setNMixtures(int v)  // before the first apply only
+    {
+        if (h_ && v != cfg_.nmixtures) throw Error(TBDK_EINVAL, "BackgroundSubtractorMOG2::setNMixtures: model allocated");
+        cfg_.nmixtures = v;
+    }
+    double getBackgroundRatio() const { return cfg_.background_ratio; }
+    void setBackgroundRatio(double v) { set(&tbdk_mog2_config::background_ratio, (float)v); }
+    double getVarThreshold() const { return cfg_.var_threshold; }
+    void setVarThreshold(double v) { set(&tbdk_mog2_config::var_threshold, v); }
+    double getVarThresholdGen() const { return cfg_.var_threshold_gen; }
+    void setVarThresholdGen(double v) { set(&tbdk_mog2_config::var_threshold_gen, (float)v); }
+    double getVarInit() const { return cfg_.var_init; }
+    void setVarInit(double v) { set(&tbdk_mog2_config::var_init, (float)v); }
+    double getVarMin() const { return cfg_.var_min; }
+    void setVarMin(double v) { set(&tbdk_mog2_config::var_min, (float)v); }
+    double getVarMax() const { return cfg_.var_max; }
+    void setVarMax(double v) { set(&tbdk_mog2_config::var_max, (float)v); }
+    double getComplexityReductionThreshold() const { return cfg_.complexity_reduction; }
+    void setComplexityReductionThreshold(double v) { set(&tbdk_mog2_config::complexity_reduction, (float)v); }
+    bool getDetectShadows() const { return cfg_.detect_shadows != 0; }
+    void setDetectShadows(bool v) { set(&tbdk_mog2_config::detect_shadows, (int32_t)(v ? 1 : 0)); }
+    int getShadowValue() const { return cfg_.shadow_value; }
+    void setShadowValue(int v) { set(&tbdk_mog2_config::shadow_value, (int32_t)(v & 255)); }  // narrowed to uchar
+    double getShadowThreshold() const { return cfg_.shadow_threshold; }
+    void setShadowThreshold(double v) { set(&tbdk_mog2_config::shadow_threshold, (float)v); }
+    tbdk_mog2* get() const { return h_; }
+
+private:
+    template <typename T>
+    void set(T tbdk_mog2_config::*field, T v)
+    {
+        const T old = cfg_.*field;
+        cfg_.*field = v;
+        if (!h_) return;
+        const int rc = tbdk_mog2_set_params(h_, &cfg_);
+        if (rc != TBDK_OK) {
+            cfg_.*field = old;
+            throw Error(rc, "tbdk_mog2_set_params");
+        }
+    }
+    Context* ctx_;
+    tbdk_mog2_config cfg_{};
+    tbdk_mog2* h_ = nullptr;
+};
+
+// cv::createBackgroundSubtractorMOG2(history, varThreshold, detectShadows)
+inline std::unique_ptr<BackgroundSubtractorMOG2> createBackgroundSubtractorMOG2(Context& ctx, int history = 500,
+                                                                                double varThreshold = 16,
+                                                                                bool detectShadows = true)
+{
+    return std::unique_ptr<BackgroundSubtractorMOG2>(new BackgroundSubtractorMOG2(ctx, history, varThreshold, detectShadows));
+}
+
 // The sample's whole per-frame path (samples/gpu/tbd.cpp:568-622) on a TbdLoop:
 // colour frame -> cvtColor -> optional resize -> HOG detectMultiScale -> the
 // loop (tbdk_tbd_step_image).  `loop` and `ctx` must outlive it.

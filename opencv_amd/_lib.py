@@ -157,6 +157,15 @@ class Affine2D(C.Structure):
                 ("valid", C.c_int32)]
 
 
+class Mog2Config(C.Structure):
+    _fields_ = [("width", C.c_int32), ("height", C.c_int32), ("depth", C.c_int32), ("channels", C.c_int32),
+                ("history", C.c_int32), ("nmixtures", C.c_int32), ("detect_shadows", C.c_int32),
+                ("shadow_value", C.c_int32), ("var_threshold", C.c_double), ("var_threshold_gen", C.c_float),
+                ("var_init", C.c_float), ("var_min", C.c_float), ("var_max", C.c_float),
+                ("background_ratio", C.c_float), ("complexity_reduction", C.c_float),
+                ("shadow_threshold", C.c_float), ("reserved", C.c_int32)]
+
+
 class SubpixParams(C.Structure):
     _fields_ = [("win_w", C.c_int32), ("win_h", C.c_int32), ("zero_w", C.c_int32), ("zero_h", C.c_int32),
                 ("criteria", C.c_int32), ("max_count", C.c_int32), ("epsilon", C.c_double)]
@@ -320,6 +329,15 @@ SIGNATURES = {
     "tbdk_klt_tracker_device_state": (C.c_int, [C.c_void_p] + [C.POINTER(C.c_void_p)] * 5),
     "tbdk_mask_circles_u8": (C.c_int, [C.c_void_p, C.c_void_p, C.c_int, C.c_int, C.c_int, C.c_void_p, C.c_void_p,
                                        C.c_int, C.c_int, C.c_int, C.c_void_p]),
+    "tbdk_mog2_config_default": (C.c_int, [C.c_int, C.c_int, C.c_int, C.c_int, C.POINTER(Mog2Config)]),
+    "tbdk_mog2_create": (C.c_int, [C.c_void_p, C.POINTER(Mog2Config), C.POINTER(C.c_void_p)]),
+    "tbdk_mog2_destroy": (C.c_int, [C.c_void_p]),
+    "tbdk_mog2_reset": (C.c_int, [C.c_void_p]),
+    "tbdk_mog2_set_params": (C.c_int, [C.c_void_p, C.POINTER(Mog2Config)]),
+    "tbdk_mog2_apply": (C.c_int, [C.c_void_p, C.c_void_p, C.c_int, C.c_void_p, C.c_int, C.c_double, C.c_void_p]),
+    "tbdk_mog2_get_background": (C.c_int, [C.c_void_p, C.c_void_p, C.c_int, C.c_void_p]),
+    "tbdk_mog2_get_model": (C.c_int, [C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p]),
+    "tbdk_mog2_frames": (C.c_int, [C.c_void_p, C.POINTER(C.c_int)]),
     "tbdk_box_propagate": (C.c_int, [C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_int,
                                      C.c_int, C.c_void_p, C.c_void_p]),
     "tbdk_ransac_default_params": (C.c_int, [C.POINTER(RansacParams)]),

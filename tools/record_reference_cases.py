@@ -49,6 +49,7 @@ import _klt_tracker_oracle as KT  # noqa: E402
 import _remap_cases as PC  # noqa: E402
 import _homography_cases as HC  # noqa: E402
 import _affine2d_cases as AC  # noqa: E402
+import _mog2_cases as GC  # noqa: E402
 
 LIMIT = 256 * 1024
 STATES = ("default", "noavx2")
@@ -56,7 +57,7 @@ STATES = ("default", "noavx2")
 MODELLED = {"pyramid": "both", "pyrlk": "both", "warpaffine": "both", "gftt": "noavx2", "gftt_mask": "noavx2",
             "cornermaps": "noavx2", "gftt_f32": "noavx2", "subpix": "both", "gftt_frame": "noavx2",
             "circle": "both", "remap": "both", "warpperspective": "both", "farneback": "noavx2",
-            "farneback_box": "noavx2", "hog": "default", "homography": "noavx2", "affine2d": "noavx2"}
+            "farneback_box": "noavx2", "hog": "default", "homography": "noavx2", "affine2d": "noavx2", "mog2": "both"}
 
 
 class Driver:
@@ -399,6 +400,32 @@ def rec_affine2d(d):
     return cases, extra
 
 
+def rec_mog2(d):
+    """BackgroundSubtractorMOG2 over the sequences of tests/_mog2_cases.py: every frame's mask (2 bits a pixel
+    for the base rows, one CRC-32 per frame for the others) and the background images after the marked frames
+    (8-bit whole, 32F as row CRCs)"""
+    cases = []
+    rows = GC.cases()
+    assert len(rows) == GC.NCASES
+    for case in rows:
+        p, fr = GC.params(case), GC.case_frames(case)
+        n, h, w, cn = case["n"], case["h"], case["w"], case["cn"]
+        want = np.array([t + 1 in case["bg"] for t in range(n)], np.uint8)
+        _, rd = d.run("mog2", dict(a=fr, rates=case["rates"].astype(np.float64), bg=want), w=w, h=h, cn=cn, n=n,
+                      depth="8u" if fr.dtype == np.uint8 else "32f", history=p["history"], nmix=p["nmixtures"],
+                      shadows=p["detect_shadows"], sval=p["shadow_value"], vt=float(p["var_threshold"]),
+                      vtg=float(p["var_threshold_gen"]), vinit=float(p["var_init"]), vmin=float(p["var_min"]),
+                      vmax=float(p["var_max"]), bgr=float(p["background_ratio"]),
+                      ct=float(p["complexity_reduction"]), tau=float(p["shadow_threshold"]))
+        masks = rd("masks", np.uint8).reshape(n, h, w)
+        bgs = rd("bg", fr.dtype).reshape((len(case["bg"]),) + fr.shape[1:])
+        ints = dict(masks=GC.stored_masks(case, masks))
+        for k, t in enumerate(case["bg"]):
+            ints[f"bg{t}"] = GC.stored_background(bgs[k])
+        cases.append((ints, {}))
+    return cases, {}
+
+
 def rec_farneback(d, table=None):
     cases, meta = [], []
     for w, h, ps, pn, ws, flags, use_init in table or RC.FB_CASES:
@@ -500,12 +527,12 @@ RECORDERS = {"pyramid": rec_pyramid, "pyrlk": rec_pyrlk, "gftt": rec_gftt, "gftt
              "cornermaps": rec_cornermaps, "gftt_f32": rec_gftt_f32, "subpix": rec_subpix, "gftt_frame": rec_gftt_frame,
              "circle": rec_circle, "warpaffine": rec_warpaffine, "remap": rec_remap,
              "warpperspective": rec_warpperspective, "farneback": rec_farneback, "farneback_box": rec_farneback_box,
-             "hog": rec_hog, "homography": rec_homography, "affine2d": rec_affine2d}
+             "hog": rec_hog, "homography": rec_homography, "affine2d": rec_affine2d, "mog2": rec_mog2}
 # bytes up to which an output is stored whole (tests/_reference_cases.py: WHOLE_LIMIT).  The kernels are
 # compared with the box Farneback flows within a tolerance, so all six stay whole (about 7 KB under LIMIT)
 WHOLE = {"farneback": 20480, "farneback_box": 72800, "pyrlk": 1 << 20, "gftt": 1 << 20, "gftt_mask": 1 << 20,
          "hog": 16384, "subpix": 1 << 20, "gftt_frame": 1 << 20, "remap": PC.WHOLE_LIMIT,
-         "warpperspective": PC.WHOLE_LIMIT, "homography": 1 << 20, "affine2d": 1 << 20}
+         "warpperspective": PC.WHOLE_LIMIT, "homography": 1 << 20, "affine2d": 1 << 20, "mog2": 1 << 20}
 # (gftt_f32: maps above RC.WHOLE_LIMIT as row CRCs; its corner lists are far below it)
 
 
@@ -548,6 +575,8 @@ def case_label(op, i):
         return HC.label(i)
     if op == "affine2d":
         return AC.label(i)
+    if op == "mog2":
+        return GC.label(i)
     if op == "circle":
         return "centre ({}, {}) radius {}".format(*KT.CIRCLE_CASES[i])
     if op == "cornermaps":

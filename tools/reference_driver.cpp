@@ -41,6 +41,12 @@
 //                                                  -> m (6 doubles; nothing for an empty result), mask (n u8):
 //                                                  estimateAffine2D (model 0) or estimateAffinePartial2D (model 1)
 //                                                  (src, dst, mask, method, thr, iters, conf, refine); prints "valid 0|1"
+//   mog2  a= (n frames, raw) w= h= cn= depth=8u|32f n= rates= (n doubles, raw) bg= (n bytes, raw) history= nmix=
+//         shadows= sval= vt= vtg= vinit= vmin= vmax= bgr= ct= tau=
+//                                                  -> masks (n x h x w u8), bg (the frame's type, one image per
+//                                                  non-zero byte of bg=): createBackgroundSubtractorMOG2, every
+//                                                  setter, apply(frame, mask, rates[t]) per frame and
+//                                                  getBackgroundImage after the marked ones
 #include <cmath>
 #include <cstdio>
 #include <cstdlib>
@@ -54,6 +60,7 @@
 #include <opencv2/core.hpp>
 #include <opencv2/imgproc.hpp>
 #include <opencv2/objdetect.hpp>
+#include <opencv2/video/background_segm.hpp>
 #include <opencv2/video/tracking.hpp>
 
 using namespace cv;
@@ -221,8 +228,52 @@ static int run_affine2d(const std::string& out)
     return 0;
 }
 
+static int run_mog2(const std::string& out)
+{
+    const int w = iarg("w"), h = iarg("h"), cn = iarg("cn"), n = iarg("n");
+    const int type = arg("depth") == "32f" ? CV_32FC(cn) : CV_8UC(cn);
+    Mat all(n * h, w, type);
+    rd(arg("a"), all.data, all.total() * all.elemSize());
+    std::vector<double> rates(n);
+    std::vector<uchar> want(n);
+    rd(arg("rates"), rates.data(), sizeof(double) * n);
+    rd(arg("bg"), want.data(), n);
+    Ptr<BackgroundSubtractorMOG2> m = createBackgroundSubtractorMOG2(iarg("history"), darg("vt"), iarg("shadows") != 0);
+    m->setHistory(iarg("history"));
+    m->setNMixtures(iarg("nmix"));
+    m->setDetectShadows(iarg("shadows") != 0);
+    m->setShadowValue(iarg("sval"));
+    m->setVarThreshold(darg("vt"));
+    m->setVarThresholdGen(darg("vtg"));
+    m->setVarInit(darg("vinit"));
+    m->setVarMin(darg("vmin"));
+    m->setVarMax(darg("vmax"));
+    m->setBackgroundRatio(darg("bgr"));
+    m->setComplexityReductionThreshold(darg("ct"));
+    m->setShadowThreshold(darg("tau"));
+    Mat masks(n * h, w, CV_8UC1);
+    std::vector<uchar> bgs;
+    for (int t = 0; t < n; ++t) {
+        Mat mask;
+        m->apply(all.rowRange(t * h, (t + 1) * h), mask, rates[t]);
+        if (mask.type() != CV_8UC1 || mask.rows != h || mask.cols != w) throw std::runtime_error("mog2: mask type");
+        mask.copyTo(masks.rowRange(t * h, (t + 1) * h));
+        if (want[t]) {
+            Mat bg;
+            m->getBackgroundImage(bg);
+            if (bg.type() != type || bg.rows != h || bg.cols != w) throw std::runtime_error("mog2: background type");
+            Mat c = bg.isContinuous() ? bg : bg.clone();
+            bgs.insert(bgs.end(), c.data, c.data + c.total() * c.elemSize());
+        }
+    }
+    wr(out, "masks", masks);
+    wr(out, "bg", bgs.data(), bgs.size());
+    return 0;
+}
+
 static int run(const std::string& op, const std::string& out)
 {
+    if (op == "mog2") return run_mog2(out);
     if (op == "homography") return run_homography(out);
     if (op == "affine2d") return run_affine2d(out);
     const int w = iarg("w"), h = iarg("h"), cn = has("cn") ? iarg("cn") : 1;
