@@ -154,8 +154,27 @@ int tbdk_ctx_destroy(tbdk_ctx* ctx);
  *   "fb_prep_ahead" (0/1, default 1): tbdk_farneback computes every level's
  *       images and polynomial expansions on an internal stream, coarse to
  *       fine, while the coarser levels iterate on the caller's stream
- *       (results equal). */
+ *       (results equal).
+ *   "alloc_fill" (-1..255, default -1 = off): a test aid.  While 0..255, every
+ *       device allocation the library makes for the context, and for any
+ *       object created from it afterwards (pyramids, TBD loops, KLT trackers,
+ *       MOG2 subtractors, detectors, tbdk_synth_render's temporary), is filled
+ *       with that byte and the device drained before anything else uses it;
+ *       the clears the library documents (a pyramid's derivative frames, a
+ *       loop's and a tracker's state) follow the fill.  Off, an allocation is
+ *       the plain hipMalloc.  Results must not depend on the value. */
 int tbdk_ctx_set_option(tbdk_ctx* ctx, const char* name, int64_t value);
+/* A test aid: no result may depend on what the context's scratch held before
+ * a call, and this call lets a test put known content there.  It synchronises
+ * the device, fills every device buffer the context owns (the GFTT, Farneback,
+ * dense PyrLK and HOG scratch and the front end's coefficient tables) over its
+ * whole capacity with `byte` (0..255), and forgets every cache keyed by host
+ * state (the front end's table slots, HOG's uploaded cell plan and detector),
+ * so the next call builds and uploads them again.  Buffers not yet allocated
+ * are skipped.  Memory of objects (pyramids, loops, trackers, subtractors,
+ * detectors) is not touched: they keep state between calls.
+ * *bytes_filled (optional): the bytes filled. */
+int tbdk_ctx_debug_fill_scratch(tbdk_ctx* ctx, int byte, int64_t* bytes_filled);
 /*   "tbd_early_gftt" (0/1/2, default 2): the TBD loop runs GFTT over the
  *       detections that will start new tracks at the start of the step, off
  *       the critical path; 2 also over the box each existing track would get
@@ -969,8 +988,12 @@ int tbdk_cvt_color_u8(tbdk_ctx* ctx, const uint8_t* src, int width, int height, 
  * 11-bit fixed-point coefficients; both scales exactly 2 is INTER_AREA,
  * equal sizes a copy).  The per-axis coefficient tables are made on the host
  * and cached in the context by (source, destination) size: a repeated size
- * allocates and uploads nothing (a new size synchronises `stream` once and
- * uploads its tables).  dst must not alias src. */
+ * allocates, uploads and waits for nothing.  A new size synchronises `stream`
+ * once and uploads its tables; once the cache's 8 slots are taken it replaces
+ * the least recently used size and waits for the whole device first, since
+ * kernels of earlier calls, on any stream, may still read those tables: calls
+ * of one context on different streams need no ordering by the caller.
+ * dst must not alias src. */
 int tbdk_resize_linear_u8(tbdk_ctx* ctx, const uint8_t* src, int width, int height, int src_pitch, int cn,
                           uint8_t* dst, int dst_width, int dst_height, int dst_pitch, void* stream);
 /* tbdk_cvt_color_u8 (one of the four *2GRAY codes) followed by

@@ -67,6 +67,7 @@ struct FbScratch {
     // another stream waits for it before reusing the scratch
     hipStream_t last_stream = nullptr;
     hipEvent_t done = nullptr;
+    int fill = -1;  // the context's alloc_fill byte, copied by fb_reserve
 };
 
 namespace {
@@ -1171,13 +1172,14 @@ int fb_reserve(tbdk_ctx* ctx, int64_t px, int64_t tcap)
         if (!f) return TBDK_ENOMEM;
         ctx->fb = f;
     }
+    f->fill = ctx->opt_alloc_fill;
     if (px > f->cap_px) {
         (void)hipFree(f->R0);
         f->R0 = f->R1 = f->F[0] = f->F[1] = f->I = nullptr;
         f->cap_px = 0;
         float* base = nullptr;
         // R0 (5) + R1 (5) + F0 (2) + F1 (2) + I (1) planes in one allocation
-        if (hipMalloc(&base, sizeof(float) * (size_t)px * 15) != hipSuccess) return TBDK_ENOMEM;
+        if (dev_alloc(&base, sizeof(float) * (size_t)px * 15, f->fill) != hipSuccess) return TBDK_ENOMEM;
         f->R0 = base;
         f->R1 = base + px * 5;
         f->F[0] = base + px * 10;
@@ -1189,7 +1191,7 @@ int fb_reserve(tbdk_ctx* ctx, int64_t px, int64_t tcap)
         (void)hipFree(f->T);
         f->T = nullptr;
         f->cap_T = 0;
-        if (hipMalloc(&f->T, sizeof(float) * (size_t)tcap) != hipSuccess) return TBDK_ENOMEM;
+        if (dev_alloc(&f->T, sizeof(float) * (size_t)tcap, f->fill) != hipSuccess) return TBDK_ENOMEM;
         f->cap_T = tcap;
     }
     return TBDK_OK;
@@ -1212,7 +1214,7 @@ int fb_reserve_ahead(FbScratch* f, int64_t rfloats, int nlev)
         (void)hipFree(f->Rl);
         f->Rl = nullptr;
         f->cap_Rl = 0;
-        if (hipMalloc(&f->Rl, sizeof(float) * (size_t)rfloats) != hipSuccess) return TBDK_ENOMEM;
+        if (dev_alloc(&f->Rl, sizeof(float) * (size_t)rfloats, f->fill) != hipSuccess) return TBDK_ENOMEM;
         f->cap_Rl = rfloats;
     }
     return TBDK_OK;
@@ -1240,6 +1242,22 @@ void fb_create_streams(tbdk_ctx* ctx)
     if (!ctx->fb) ctx->fb = new (std::nothrow) FbScratch();
     FbScratch* f = ctx->fb;
     if (f && !f->prep && hipStreamCreateWithFlags(&f->prep, hipStreamNonBlocking) != hipSuccess) f->prep = nullptr;
+}
+
+hipError_t fb_debug_fill(tbdk_ctx* ctx, int byte, int64_t* bytes)
+{
+    FbScratch* f = ctx->fb;
+    if (!f) return hipSuccess;
+    const std::pair<void*, size_t> bufs[] = {{f->R0, sizeof(float) * (size_t)f->cap_px * 15},
+                                             {f->T, sizeof(float) * (size_t)f->cap_T},
+                                             {f->Rl, sizeof(float) * (size_t)f->cap_Rl}};
+    for (const auto& b : bufs) {
+        if (!b.first) continue;
+        const hipError_t e = hipMemset(b.first, byte, b.second);
+        if (e != hipSuccess) return e;
+        *bytes += (int64_t)b.second;
+    }
+    return hipSuccess;
 }
 
 void fb_release(tbdk_ctx* ctx)

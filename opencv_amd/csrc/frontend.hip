@@ -273,10 +273,13 @@ void make_ytab(int sh, int dh, YTap* out)
 }  // namespace
 
 // The context's table cache: a few (source, destination) size pairs, each with
-// its device tables.  A repeated size allocates and uploads nothing.  A new size
-// takes the least recently used slot after synchronising the calling stream,
-// like the HOG scratch: calls of one context on different streams with more live
-// sizes than slots must be ordered by the caller.
+// its device tables.  A repeated size allocates, uploads and waits for nothing.
+// A new size takes the least recently used slot.  A slot that held tables before
+// may still be read by kernels of earlier calls, on any stream the caller used
+// (a hit records nothing, so the slot does not know its readers): the eviction
+// drains the device before it overwrites the tables in place, so calls of one
+// context on different streams need no ordering by the caller, however many
+// sizes are live.
 struct FrontScratch {
     static constexpr int kSlots = 8;
     struct Slot {
@@ -302,6 +305,27 @@ void front_release(tbdk_ctx* ctx)
     ctx->front = nullptr;
 }
 
+// the slots' tables over their capacity; every key forgotten, so the next call
+// of any size builds and uploads its tables again
+hipError_t front_debug_fill(tbdk_ctx* ctx, int byte, int64_t* bytes)
+{
+    FrontScratch* F = ctx->front;
+    if (!F) return hipSuccess;
+    std::lock_guard<std::mutex> lk(F->mu);
+    for (auto& sl : F->slot) {
+        sl.sw = sl.sh = sl.dw = sl.dh = 0;
+        const std::pair<void*, size_t> bufs[] = {{sl.xt, sizeof(XTap) * (size_t)sl.cap_x},
+                                                 {sl.yt, sizeof(YTap) * (size_t)sl.cap_y}};
+        for (const auto& b : bufs) {
+            if (!b.first || !b.second) continue;
+            const hipError_t e = hipMemset(b.first, byte, b.second);
+            if (e != hipSuccess) return e;
+            *bytes += (int64_t)b.second;
+        }
+    }
+    return hipSuccess;
+}
+
 namespace {
 
 int front_tables(tbdk_ctx* ctx, int sw, int sh, int dw, int dh, const XTap** xt, const YTap** yt, hipStream_t s)
@@ -322,14 +346,14 @@ int front_tables(tbdk_ctx* ctx, int sw, int sh, int dw, int dh, const XTap** xt,
     if (pick->cap_x < dw) {
         if (pick->xt) (void)hipFree(pick->xt);
         pick->xt = nullptr, pick->cap_x = 0;
-        if (hipMalloc(reinterpret_cast<void**>(&pick->xt), sizeof(XTap) * (size_t)dw) != hipSuccess) return TBDK_ENOMEM;
+        if (dev_alloc(&pick->xt, sizeof(XTap) * (size_t)dw, ctx->opt_alloc_fill) != hipSuccess) return TBDK_ENOMEM;
         pick->cap_x = dw;
     }
     if (pick->cap_y < dh) {
         if (pick->yt) (void)hipFree(pick->yt);
         pick->yt = nullptr, pick->cap_y = 0;
         pick->sw = 0;  // not a valid entry until both tables exist
-        if (hipMalloc(reinterpret_cast<void**>(&pick->yt), sizeof(YTap) * (size_t)dh) != hipSuccess) return TBDK_ENOMEM;
+        if (dev_alloc(&pick->yt, sizeof(YTap) * (size_t)dh, ctx->opt_alloc_fill) != hipSuccess) return TBDK_ENOMEM;
         pick->cap_y = dh;
     }
     std::vector<XTap> hx((size_t)dw);
@@ -337,9 +361,10 @@ int front_tables(tbdk_ctx* ctx, int sw, int sh, int dw, int dh, const XTap** xt,
     make_xtab(sw, dw, hx.data());
     make_ytab(sh, dh, hy.data());
     pick->sw = 0;
-    // a new size only: wait for the stream's earlier readers of this slot, then
-    // copy before returning (the host tables are locals)
-    hipError_t e = hipStreamSynchronize(s);
+    // a new size only: wait for the earlier readers of this slot, whatever their
+    // stream (a slot never used has none), then copy before returning (the host
+    // tables are locals)
+    hipError_t e = pick->used ? hipDeviceSynchronize() : hipStreamSynchronize(s);
     if (e == hipSuccess) e = hipMemcpy(pick->xt, hx.data(), sizeof(XTap) * (size_t)dw, hipMemcpyHostToDevice);
     if (e == hipSuccess) e = hipMemcpy(pick->yt, hy.data(), sizeof(YTap) * (size_t)dh, hipMemcpyHostToDevice);
     if (e != hipSuccess) return map_status(e);

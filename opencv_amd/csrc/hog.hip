@@ -71,6 +71,7 @@ struct HogScratch {
     float* lane_grad[kMaxLanes] = {};
     uint8_t* lane_qangle[kMaxLanes] = {};
     int64_t lane_cap_px[kMaxLanes] = {};
+    int fill = -1;  // the context's alloc_fill byte, copied by reserve()
 };
 
 // The scratch (cell table, level image, gradients, blocks, hits) is rewritten by
@@ -803,13 +804,13 @@ static void cell_lists(const tbdk_hog_params* p, std::vector<std::vector<int4>>&
 }
 
 template <typename T>
-static int grow(T** p, int64_t& cap, int64_t need)
+static int grow(T** p, int64_t& cap, int64_t need, int fill)
 {
     if (need <= cap) return TBDK_OK;
     if (*p) (void)hipFree(*p);
     *p = nullptr;
     cap = 0;
-    if (hipMalloc(reinterpret_cast<void**>(p), sizeof(T) * (size_t)need) != hipSuccess) return TBDK_ENOMEM;
+    if (dev_alloc(p, sizeof(T) * (size_t)need, fill) != hipSuccess) return TBDK_ENOMEM;
     cap = need;
     return TBDK_OK;
 }
@@ -998,24 +999,26 @@ static int reserve(tbdk_ctx* ctx, int w, int h, int cn, const HogPlan& pl, int s
     if (!S) return TBDK_ENOMEM;
     if (claim(S, s) != hipSuccess) return TBDK_EHIP;
     S->block_tiled = ctx->opt_hog_block_tiled;
+    S->fill = ctx->opt_alloc_fill;
     const int64_t px = (int64_t)w * h;
     int rc = TBDK_OK;
     if (px > S->cap_px) {
         int64_t c0 = 0, c1 = 0, c2 = 0;
-        if ((rc = grow(&S->level, c0, px * 4)) || (rc = grow(&S->grad, c1, px * 2)) ||
-            (rc = grow(&S->qangle, c2, px * 2)))
+        if ((rc = grow(&S->level, c0, px * 4, S->fill)) || (rc = grow(&S->grad, c1, px * 2, S->fill)) ||
+            (rc = grow(&S->qangle, c2, px * 2, S->fill)))
             return rc;
         S->cap_px = px;
     }
     const int64_t nblk = ((int64_t)w / pl.csx + 1) * (h / pl.csy + 1) * pl.hsz;
-    if ((rc = grow(&S->blocks, S->cap_blocks, nblk))) return rc;
+    if ((rc = grow(&S->blocks, S->cap_blocks, nblk, S->fill))) return rc;
     if (svm_len > S->cap_svm) S->svm_host.clear();  // reallocated below: contents unknown
-    if ((rc = grow(&S->svm, S->cap_svm, svm_len))) return rc;
+    if ((rc = grow(&S->svm, S->cap_svm, svm_len, S->fill))) return rc;
     if ((int64_t)pl.ncells * pl.cell_cap > S->cap_cells) S->cells_host.clear();
-    if ((rc = grow(&S->cells, S->cap_cells, (int64_t)pl.ncells * pl.cell_cap))) return rc;
+    if ((rc = grow(&S->cells, S->cap_cells, (int64_t)pl.ncells * pl.cell_cap, S->fill))) return rc;
     if (hit_cap > S->cap_hits) {
         int64_t c = 0;
-        if ((rc = grow(&S->hits, c, 1 + 3 * hit_cap)) || (rc = grow(&S->scores, S->cap_hits, hit_cap))) return rc;
+        if ((rc = grow(&S->hits, c, 1 + 3 * hit_cap, S->fill)) || (rc = grow(&S->scores, S->cap_hits, hit_cap, S->fill)))
+            return rc;
     }
     (void)cn;
     return TBDK_OK;
@@ -1150,8 +1153,8 @@ static int reserve_lanes(HogScratch* S, int n, int64_t px)
         if (px <= S->lane_cap_px[k]) continue;
         int64_t c0 = 0, c1 = 0, c2 = 0;
         S->lane_cap_px[k] = 0;
-        if ((rc = grow(&S->lane_level[k], c0, px * 4)) || (rc = grow(&S->lane_grad[k], c1, px * 2)) ||
-            (rc = grow(&S->lane_qangle[k], c2, px * 2)))
+        if ((rc = grow(&S->lane_level[k], c0, px * 4, S->fill)) || (rc = grow(&S->lane_grad[k], c1, px * 2, S->fill)) ||
+            (rc = grow(&S->lane_qangle[k], c2, px * 2, S->fill)))
             return rc;
         S->lane_cap_px[k] = px;
     }
@@ -1200,6 +1203,39 @@ void tbdk::hog_create_lanes(tbdk_ctx* ctx)
 {
     if (!ctx->hog) ctx->hog = new (std::nothrow) HogScratch();
     if (ctx->hog) (void)create_lanes(ctx->hog, std::min(ctx->opt_hog_level_streams, HogScratch::kMaxLanes));
+}
+
+// every buffer over its whole capacity; the host copies of `cells` and `svm`
+// forgotten, so the next call uploads both again
+hipError_t tbdk::hog_debug_fill(tbdk_ctx* ctx, int byte, int64_t* bytes)
+{
+    HogScratch* S = ctx->hog;
+    if (!S) return hipSuccess;
+    S->cells_host.clear();
+    S->svm_host.clear();
+    std::vector<std::pair<void*, size_t>> bufs = {
+        {S->level, (size_t)S->cap_px * 4},
+        {S->grad, sizeof(float) * (size_t)S->cap_px * 2},
+        {S->qangle, (size_t)S->cap_px * 2},
+        {S->blocks, sizeof(float) * (size_t)S->cap_blocks},
+        {S->svm, sizeof(float) * (size_t)S->cap_svm},
+        {S->cells, sizeof(int4) * (size_t)S->cap_cells},
+        {S->hits, sizeof(int) * (size_t)(1 + 3 * S->cap_hits)},
+        {S->scores, sizeof(double) * (size_t)S->cap_hits},
+        {S->mblocks, sizeof(float) * (size_t)S->cap_mblocks},
+        {S->lvtab, sizeof(HogLevelEnt) * (size_t)S->cap_lvtab}};
+    for (int k = 1; k < HogScratch::kMaxLanes; ++k) {
+        bufs.push_back({S->lane_level[k], (size_t)S->lane_cap_px[k] * 4});
+        bufs.push_back({S->lane_grad[k], sizeof(float) * (size_t)S->lane_cap_px[k] * 2});
+        bufs.push_back({S->lane_qangle[k], (size_t)S->lane_cap_px[k] * 2});
+    }
+    for (const auto& b : bufs) {
+        if (!b.first || !b.second) continue;
+        const hipError_t e = hipMemset(b.first, byte, b.second);
+        if (e != hipSuccess) return e;
+        *bytes += (int64_t)b.second;
+    }
+    return hipSuccess;
 }
 
 void tbdk::hog_release(tbdk_ctx* ctx)
@@ -1401,8 +1437,8 @@ int tbdk_hog_detect_multiscale(tbdk_ctx* ctx, const uint8_t* img, int width, int
         nwwg += win_tiled ? en.nwy * ((en.nwx + kHogWinTile - 1) / kHogWinTile)
                           : (en.nwx * en.nwy + kHogWinPerWg - 1) / kHogWinPerWg;
     }
-    if ((rc = grow(&S->mblocks, S->cap_mblocks, std::max<int64_t>(boff, 1))) ||
-        (rc = grow(&S->lvtab, S->cap_lvtab, std::max<int64_t>((int64_t)ents.size(), 1))))
+    if ((rc = grow(&S->mblocks, S->cap_mblocks, std::max<int64_t>(boff, 1), S->fill)) ||
+        (rc = grow(&S->lvtab, S->cap_lvtab, std::max<int64_t>((int64_t)ents.size(), 1), S->fill)))
         return rc;
     hipError_t e = ents.empty() ? hipSuccess
                                 : hipMemcpyAsync(S->lvtab, ents.data(), sizeof(HogLevelEnt) * ents.size(),

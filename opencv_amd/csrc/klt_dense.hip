@@ -148,7 +148,7 @@ int tbdk_lk_dense(tbdk_ctx* ctx, const tbdk_pyr* prev, const tbdk_pyr* next, flo
             if (ctx->dcase_buf) (void)hipFree(ctx->dcase_buf);
             ctx->dcase_buf = nullptr;
             ctx->dcase_cap = 0;
-            if (hipMalloc(&ctx->dcase_buf, bytes) != hipSuccess) return TBDK_ENOMEM;
+            if (dev_alloc(&ctx->dcase_buf, bytes, ctx->opt_alloc_fill) != hipSuccess) return TBDK_ENOMEM;
             ctx->dcase_cap = bytes;
         }
         uint2* base = static_cast<uint2*>(ctx->dcase_buf);
@@ -188,7 +188,7 @@ int tbdk_lk_dense(tbdk_ctx* ctx, const tbdk_pyr* prev, const tbdk_pyr* next, flo
         if (ctx->dense_buf) (void)hipFree(ctx->dense_buf);
         ctx->dense_buf = nullptr;
         ctx->dense_cap = 0;
-        if (hipMalloc(&ctx->dense_buf, (size_t)n * 17 + 256) != hipSuccess) return TBDK_ENOMEM;
+        if (dev_alloc(&ctx->dense_buf, (size_t)n * 17 + 256, ctx->opt_alloc_fill) != hipSuccess) return TBDK_ENOMEM;
         ctx->dense_cap = n;
     }
     float2* pts = static_cast<float2*>(ctx->dense_buf);

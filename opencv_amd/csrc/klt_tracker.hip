@@ -361,6 +361,7 @@ int tbdk_klt_tracker_create(tbdk_ctx* ctx, const tbdk_klt_tracker_config* cfg, t
         return rc;
     }
     DeviceGuard g(ctx->device);
+    t->gftt.fill = ctx->opt_alloc_fill;
     rc = tbdk_pyr_create_levels(ctx, c.width, c.height, c.max_level, c.win, c.win, &t->pyr[0]);
     if (rc == TBDK_OK) rc = tbdk_pyr_create_levels(ctx, c.width, c.height, c.max_level, c.win, c.win, &t->pyr[1]);
     // GFTT scratch for the whole-frame ROI, the wide selection's and the response planes' included
@@ -381,7 +382,7 @@ int tbdk_klt_tracker_create(tbdk_ctx* ctx, const tbdk_klt_tracker_config* cfg, t
             off[i] = total;
             total += up256(sizes[i]);
         }
-        rc = map_status(hipMalloc(&t->mem, total));
+        rc = map_status(dev_alloc(&t->mem, total, ctx->opt_alloc_fill));
         if (rc == TBDK_OK) {
             t->mem_bytes = total;
             uint8_t* b = static_cast<uint8_t*>(t->mem);

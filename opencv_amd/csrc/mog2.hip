@@ -438,7 +438,7 @@ int tbdk_mog2_create(tbdk_ctx* ctx, const tbdk_mog2_config* cfg, tbdk_mog2** out
     const size_t K = (size_t)c.nmixtures, cn = (size_t)c.channels, ps = (size_t)p.ps;
     m->mem_bytes = K * ps * 4 * (2 + cn) + ps;
     DeviceGuard g(ctx->device);
-    const int rc = map_status(hipMalloc(&m->mem, m->mem_bytes));
+    const int rc = map_status(dev_alloc(&m->mem, m->mem_bytes, ctx->opt_alloc_fill));
     if (rc != TBDK_OK) {
         delete m;
         return rc;

@@ -85,6 +85,40 @@ static int map_err(hipError_t e)
 
 int map_status(hipError_t e) { return map_err(e); }
 
+hipError_t dev_alloc(void** p, size_t bytes, int fill)
+{
+    hipError_t e = hipMalloc(p, bytes);
+    if (fill < 0 || e != hipSuccess) return e;
+    e = hipMemset(*p, fill, bytes);
+    if (e == hipSuccess) e = hipDeviceSynchronize();
+    if (e != hipSuccess) {
+        (void)hipFree(*p);
+        *p = nullptr;
+    }
+    return e;
+}
+
+hipError_t gftt_debug_fill(GfttScratch& sc, int byte, int64_t* bytes)
+{
+    const int64_t ncb = gftt_max_cblocks(std::max(sc.cap_rois, 0), sc.cap_px), nw = gftt_max_words(sc.cap_px);
+    const std::pair<void*, size_t> bufs[] = {
+        {sc.rois, sizeof(GfttRoi) * (size_t)std::max(sc.cap_rois, 1)},
+        {sc.blk, sizeof(int) * (size_t)ncb},
+        {sc.planes, sizeof(float) * (size_t)std::max<int64_t>(sc.cap_px, 1)},
+        {sc.cand, sizeof(uint64_t) * (size_t)nw},
+        {sc.resp, (sizeof(float) * 3 + sizeof(double) * 3) * (size_t)std::max<int64_t>(sc.cap_resp_px, 1)},
+        {sc.wide_keys, 2 * sizeof(uint64_t) * (size_t)std::max<int64_t>(sc.cap_wide_px, 1)},
+        {sc.wide_cells, sizeof(uint32_t) * (size_t)std::max<int64_t>(sc.cap_wide_px, 1)},
+        {sc.wide_state, sizeof(GfttWideState) * (size_t)std::max(sc.cap_wide_rois, 1)}};
+    for (const auto& b : bufs) {
+        if (!b.first) continue;
+        const hipError_t e = hipMemset(b.first, byte, b.second);
+        if (e != hipSuccess) return e;
+        *bytes += (int64_t)b.second;
+    }
+    return hipSuccess;
+}
+
 }  // namespace tbdk
 
 using namespace tbdk;
@@ -161,6 +195,12 @@ int tbdk_ctx_set_option(tbdk_ctx* ctx, const char* name, int64_t value)
     if (!ctx || !name) return TBDK_EINVAL;
     if (std::strcmp(name, "gftt_eig_redo") == 0) {
         ctx->opt_gftt_eig_redo = value != 0;
+        return TBDK_OK;
+    }
+    if (std::strcmp(name, "alloc_fill") == 0) {  // test aid: see tbdk.h
+        if (value < -1 || value > 255) return TBDK_EINVAL;
+        ctx->opt_alloc_fill = (int)value;
+        ctx->gftt.fill = (int)value;
         return TBDK_OK;
     }
     if (std::strcmp(name, "gftt_wide") == 0) {
@@ -308,6 +348,29 @@ int tbdk_ctx_set_option(tbdk_ctx* ctx, const char* name, int64_t value)
     return TBDK_EINVAL;
 }
 
+int tbdk_ctx_debug_fill_scratch(tbdk_ctx* ctx, int byte, int64_t* bytes_filled)
+{
+    if (!ctx || byte < 0 || byte > 255) return TBDK_EINVAL;
+    DeviceGuard g(ctx->device);
+    int64_t n = 0;
+    hipError_t e = hipDeviceSynchronize();
+    if (e == hipSuccess) e = gftt_debug_fill(ctx->gftt, byte, &n);
+    if (e == hipSuccess) e = fb_debug_fill(ctx, byte, &n);
+    if (e == hipSuccess) e = hog_debug_fill(ctx, byte, &n);
+    if (e == hipSuccess) e = front_debug_fill(ctx, byte, &n);
+    if (e == hipSuccess && ctx->dense_buf) {
+        e = hipMemset(ctx->dense_buf, byte, (size_t)ctx->dense_cap * 17 + 256);
+        n += ctx->dense_cap * 17 + 256;
+    }
+    if (e == hipSuccess && ctx->dcase_buf) {
+        e = hipMemset(ctx->dcase_buf, byte, ctx->dcase_cap);
+        n += (int64_t)ctx->dcase_cap;
+    }
+    if (e == hipSuccess) e = hipDeviceSynchronize();
+    if (bytes_filled) *bytes_filled = n;
+    return map_err(e);
+}
+
 int tbdk_timing_select(tbdk_ctx* ctx, const char* names)
 {
     if (!ctx) return TBDK_EINVAL;
@@ -397,11 +460,19 @@ static int pyr_create(tbdk_ctx* ctx, int width, int height, int max_level, int w
         if (w <= win_w || h <= win_h) break;
     }
     void* mem = nullptr;
-    hipError_t e = hipMalloc(&mem, total);
+    hipError_t e = dev_alloc(&mem, total, ctx->opt_alloc_fill);
     if (e != hipSuccess) return map_err(e);
     // the derivative planes' BORDER_CONSTANT frame is zero once and never rewritten
-    // (levels only: every byte a reader can reach is rewritten by each build)
-    e = hipMemset(mem, 0, total);
+    // (levels only: every byte a reader can reach is rewritten by each build, so
+    // under alloc_fill the levels keep the fill byte and only the planes are cleared)
+    if (ctx->opt_alloc_fill < 0) {
+        e = hipMemset(mem, 0, total);
+    } else {
+        for (int level = 0; level < nlev && e == hipSuccess && !(flags & TBDK_PYR_NO_DERIVS); ++level)
+            e = hipMemset(static_cast<uint8_t*>(mem) + doffs[level], 0,
+                          (size_t)pyr->dv[level].pitch * (pyr->dv[level].height + 2 * pad) + 256);
+        if (e == hipSuccess) e = hipDeviceSynchronize();
+    }
     if (e != hipSuccess) {
         (void)hipFree(mem);
         return map_err(e);
@@ -910,9 +981,9 @@ int gftt_reserve_wide(GfttScratch& sc, int device, int max_rois, int64_t max_px)
     }
     sc.cap_wide_rois = 0;
     sc.cap_wide_px = 0;
-    hipError_t e = hipMalloc(&sc.wide_keys, 2 * sizeof(uint64_t) * (size_t)std::max<int64_t>(px, 1));
-    if (e == hipSuccess) e = hipMalloc(&sc.wide_cells, sizeof(uint32_t) * (size_t)std::max<int64_t>(px, 1));
-    if (e == hipSuccess) e = hipMalloc(&sc.wide_state, sizeof(GfttWideState) * (size_t)std::max(rois, 1));
+    hipError_t e = dev_alloc(&sc.wide_keys, 2 * sizeof(uint64_t) * (size_t)std::max<int64_t>(px, 1), sc.fill);
+    if (e == hipSuccess) e = dev_alloc(&sc.wide_cells, sizeof(uint32_t) * (size_t)std::max<int64_t>(px, 1), sc.fill);
+    if (e == hipSuccess) e = dev_alloc(&sc.wide_state, sizeof(GfttWideState) * (size_t)std::max(rois, 1), sc.fill);
     if (e != hipSuccess) {
         for (void** p : {&sc.wide_keys, &sc.wide_cells, &sc.wide_state}) {
             if (*p) (void)hipFree(*p);
@@ -932,7 +1003,7 @@ int gftt_reserve_resp(GfttScratch& sc, int device, int64_t max_px)
     if (sc.resp) (void)hipFree(sc.resp);  // waits for the device: no launch still reads it
     sc.resp = nullptr;
     sc.cap_resp_px = 0;
-    const hipError_t e = hipMalloc(&sc.resp, (sizeof(float) * 3 + sizeof(double) * 3) * (size_t)std::max<int64_t>(max_px, 1));
+    const hipError_t e = dev_alloc(&sc.resp, (sizeof(float) * 3 + sizeof(double) * 3) * (size_t)std::max<int64_t>(max_px, 1), sc.fill);
     if (e != hipSuccess) return map_err(e);
     sc.cap_resp_px = max_px;
     return TBDK_OK;
@@ -947,10 +1018,10 @@ int gftt_reserve(GfttScratch& sc, int device, int max_rois, int64_t max_px)
     const int64_t px = std::max(max_px, sc.cap_px);
     gftt_scratch_free(sc);  // hipFree waits for the device: no launch still reads it
     const int64_t ncb = gftt_max_cblocks(rois, px), nw = gftt_max_words(px);
-    hipError_t e = hipMalloc(&sc.rois, sizeof(GfttRoi) * (size_t)std::max(rois, 1));
-    if (e == hipSuccess) e = hipMalloc(reinterpret_cast<void**>(&sc.blk), sizeof(int) * (size_t)ncb);
-    if (e == hipSuccess) e = hipMalloc(&sc.planes, sizeof(float) * (size_t)std::max<int64_t>(px, 1));
-    if (e == hipSuccess) e = hipMalloc(&sc.cand, sizeof(uint64_t) * (size_t)nw);
+    hipError_t e = dev_alloc(&sc.rois, sizeof(GfttRoi) * (size_t)std::max(rois, 1), sc.fill);
+    if (e == hipSuccess) e = dev_alloc(&sc.blk, sizeof(int) * (size_t)ncb, sc.fill);
+    if (e == hipSuccess) e = dev_alloc(&sc.planes, sizeof(float) * (size_t)std::max<int64_t>(px, 1), sc.fill);
+    if (e == hipSuccess) e = dev_alloc(&sc.cand, sizeof(uint64_t) * (size_t)nw, sc.fill);
     if (e != hipSuccess) {
         gftt_scratch_free(sc);
         return map_err(e);
@@ -1344,7 +1415,7 @@ int tbdk_synth_render(tbdk_ctx* ctx, uint32_t seed, int width, int height, int n
             }
         }
     void* dposes = nullptr;
-    hipError_t e = hipMalloc(&dposes, sizeof(syn_pose) * (size_t)nob * nframes);
+    hipError_t e = dev_alloc(&dposes, sizeof(syn_pose) * (size_t)nob * nframes, ctx->opt_alloc_fill);
     if (e == hipSuccess)
         e = hipMemcpyAsync(dposes, poses, sizeof(syn_pose) * (size_t)nob * nframes, hipMemcpyHostToDevice, s);
     uint32_t bgseed = syn_hash(seed ^ 0xB6A5EEDU);

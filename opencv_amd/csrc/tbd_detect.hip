@@ -79,11 +79,11 @@ int tbdk_tbd_detector_create(tbdk_ctx* ctx, tbdk_tbd* tbd, const tbdk_tbd_detect
     hipError_t e = hipSuccess;
     if (cfg->src_cn != 1 || resized) {  // gray frames of the loop's size are used in place
         d->gray_pitch = align_up(cfg->width, 64);
-        e = hipMalloc(reinterpret_cast<void**>(&d->gray), (size_t)d->gray_pitch * cfg->height);
+        e = dev_alloc(&d->gray, (size_t)d->gray_pitch * cfg->height, ctx->opt_alloc_fill);
     }
     if (e == hipSuccess && cfg->src_cn != 1 && !cfg->make_gray && resized) {
         d->color_pitch = align_up(cfg->width * cfg->src_cn, 64);
-        e = hipMalloc(reinterpret_cast<void**>(&d->color), (size_t)d->color_pitch * cfg->height);
+        e = dev_alloc(&d->color, (size_t)d->color_pitch * cfg->height, ctx->opt_alloc_fill);
     }
     if (e != hipSuccess) {
         (void)tbdk_tbd_detector_destroy(d);
@@ -241,7 +241,7 @@ int tbdk_app_run_images(const tbdk_app_image_args* a, tbdk_app_image_result* res
         (rc = tbdk_tbd_set_trajectories(tbd, traj)) == TBDK_OK &&
         (rc = tbdk_tbd_detector_create(ctx, tbd, &dc, a->svm, a->svm_len, &det)) == TBDK_OK) {
         DeviceGuard g(a->device);
-        rc = map_status(hipMalloc(reinterpret_cast<void**>(&dframe), (size_t)fpitch * first.height));
+        rc = map_status(dev_alloc(&dframe, (size_t)fpitch * first.height, ctx->opt_alloc_fill));
         for (size_t i = 0; i < paths.size() && rc == TBDK_OK; ++i) {
             PnmInfo pi;
             if (pnm_read_file(paths[i], file, &pi) != kPnmOk || pi.width != first.width || pi.height != first.height ||

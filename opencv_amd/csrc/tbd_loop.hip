@@ -589,7 +589,7 @@ int tbdk_tbd_create(tbdk_ctx* ctx, const tbdk_tbd_config* cfg, tbdk_tbd** out)
     const size_t S = (size_t)cfg->max_tracks;
     hipError_t e = hipSuccess;
     auto dm = [&](void** p, size_t bytes) {
-        if (e == hipSuccess) e = hipMalloc(p, bytes);
+        if (e == hipSuccess) e = dev_alloc(p, bytes, ctx->opt_alloc_fill);
         if (e == hipSuccess) e = hipMemset(*p, 0, bytes);
     };
     t->zc = ctx->opt_tbd_zero_copy != 0;
@@ -713,6 +713,7 @@ int tbdk_tbd_create(tbdk_ctx* ctx, const tbdk_tbd_config* cfg, tbdk_tbd** out)
     t->npts_of = FlatMap<unsigned>(4 * (size_t)cfg->max_tracks);
     t->erow_of = FlatMap<uint64_t>(4 * (size_t)cfg->max_tracks);
     t->ahead_row_of = FlatMap<uint64_t>(4 * (size_t)cfg->max_tracks);
+    t->gftt.fill = t->gftt2.fill = ctx->opt_alloc_fill;
     rc = gftt_reserve(t->gftt, ctx->device, cfg->max_tracks, (int64_t)cfg->width * cfg->height * 2);
     if (rc == TBDK_OK) rc = gftt_reserve(t->gftt2, ctx->device, cfg->max_tracks, (int64_t)cfg->width * cfg->height * 2);
     if (rc != TBDK_OK) {
@@ -1615,7 +1616,7 @@ int tbdk_tbd_run_host(tbdk_tbd* t, const uint8_t* const* frames, int pitch, int 
     if (!t->up_s) {  // the ring, its stream and events: once per loop
         t->ring_pitch = (W + 255) & ~255;
         for (int k = 0; k < 3 && e == hipSuccess; ++k) {
-            e = hipMalloc(reinterpret_cast<void**>(&t->ring[k]), (size_t)t->ring_pitch * H + 256);
+            e = dev_alloc(&t->ring[k], (size_t)t->ring_pitch * H + 256, t->ctx->opt_alloc_fill);
             if (e == hipSuccess) e = hipEventCreateWithFlags(&t->copied[k], hipEventDisableTiming);
             if (e == hipSuccess) e = hipEventCreateWithFlags(&t->freed[k], hipEventDisableTiming);
         }

@@ -71,6 +71,7 @@ struct GfttScratch {
     void* wide_state = nullptr;  // GfttWideState[cap_wide_rois]
     int cap_wide_rois = 0;
     int64_t cap_wide_px = 0;
+    int fill = -1;  // the owner's alloc_fill byte (the reserve functions have no context at hand)
 };
 struct HogScratch;  // hog.hip
 struct FrontScratch;  // frontend.hip
@@ -114,6 +115,7 @@ struct tbdk_ctx {
     int opt_tbd_fit_ransac = 0;  // tbdk_ctx_set_option("tbd_fit_ransac"): RANSAC rounds of the loop's fit, 0 = least squares (read by tbdk_tbd_create)
     int opt_tbd_fb_check = 0;    // tbdk_ctx_set_option("tbd_fb_check"): the loop's forward-backward check, threshold in 1/1024 px, 0 = off (read by tbdk_tbd_create)
     int opt_tbd_subpix = 0;      // tbdk_ctx_set_option("tbd_subpix"): the loop refines its GFTT corners, window half size, 0 = off (read by tbdk_tbd_create)
+    int opt_alloc_fill = -1;     // tbdk_ctx_set_option("alloc_fill"): test aid, every new device allocation filled with this byte (-1: off)
     int opt_gftt_wide = 0;       // tbdk_ctx_set_option("gftt_wide"): 0 = the wide selection where the LDS one cannot serve, 1 = for every ROI
     std::string timing_only;  // ",name,name," filter of tbdk_timing_select ("" = all)
     int timing_every = 1;     // tbdk_ctx_set_option("timing_every"): events on every Nth selected launch
@@ -147,6 +149,23 @@ namespace tbdk {
 // RAII-free helpers used by the C-ABI around each launch.
 int timing_begin(tbdk_ctx* ctx, const char* name, hipStream_t s);
 void timing_end(tbdk_ctx* ctx, int rec, hipStream_t s);
+
+// Every device allocation of the library.  fill < 0: hipMalloc and nothing
+// else.  fill 0..255 (ctx option alloc_fill, a test aid): the block is filled
+// with that byte and the device drained before anything else can use it.
+hipError_t dev_alloc(void** p, size_t bytes, int fill);
+template <typename T>
+inline hipError_t dev_alloc(T** p, size_t bytes, int fill)
+{
+    return dev_alloc(reinterpret_cast<void**>(p), bytes, fill);
+}
+// tbdk_ctx_debug_fill_scratch's parts: fill what the context owns there over
+// its whole capacity, forget the caches, add the bytes filled (device drained
+// by the caller)
+hipError_t gftt_debug_fill(GfttScratch& sc, int byte, int64_t* bytes);
+hipError_t fb_debug_fill(tbdk_ctx* ctx, int byte, int64_t* bytes);
+hipError_t hog_debug_fill(tbdk_ctx* ctx, int byte, int64_t* bytes);
+hipError_t front_debug_fill(tbdk_ctx* ctx, int byte, int64_t* bytes);
 
 // frees the context's Farneback scratch (farneback.hip)
 void fb_release(tbdk_ctx* ctx);

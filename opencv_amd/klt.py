@@ -45,6 +45,10 @@ class Context:
         self.device = int(device)
 
     def __del__(self):
+        self.close()
+
+    def close(self) -> None:
+        """tbdk_ctx_destroy; every object made from the context must be gone by then."""
         h = getattr(self, "handle", None)
         if h and h.value:
             try:
@@ -67,6 +71,14 @@ class Context:
     def set_option(self, name: str, value: int) -> None:
         """tbdk_ctx_set_option (see include/tbdk.h)."""
         _lib.check(self.lib.tbdk_ctx_set_option(self.handle, name.encode(), int(value)), "tbdk_ctx_set_option")
+
+    def debug_fill_scratch(self, byte: int) -> int:
+        """tbdk_ctx_debug_fill_scratch (a test aid, see include/tbdk.h): every device
+        buffer the context owns filled with `byte`, every cache forgotten; the bytes filled."""
+        n = C.c_int64()
+        _lib.check(self.lib.tbdk_ctx_debug_fill_scratch(self.handle, int(byte), C.byref(n)),
+                   "tbdk_ctx_debug_fill_scratch")
+        return int(n.value)
 
     def timing_select(self, names=None) -> None:
         """Record only these kernels (iterable of names; None = all)."""
