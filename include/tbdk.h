@@ -167,7 +167,8 @@ int tbdk_ctx_set_option(tbdk_ctx* ctx, const char* name, int64_t value);
 /* A test aid: no result may depend on what the context's scratch held before
  * a call, and this call lets a test put known content there.  It synchronises
  * the device, fills every device buffer the context owns (the GFTT, Farneback,
- * dense PyrLK and HOG scratch and the front end's coefficient tables) over its
+ * dense PyrLK, HOG, morphology and connected-components scratch and the front
+ * end's coefficient tables) over its
  * whole capacity with `byte` (0..255), and forgets every cache keyed by host
  * state (the front end's table slots, HOG's uploaded cell plan and detector),
  * so the next call builds and uploads them again.  Buffers not yet allocated
@@ -1644,6 +1645,84 @@ int tbdk_mog2_get_model(tbdk_mog2* m, float* weight, float* variance, float* mea
                         void* stream);
 /* frames applied since the model was last cleared */
 int tbdk_mog2_frames(tbdk_mog2* m, int* nframes);
+
+/* ---- morphology and connected components ----------------------------------- */
+
+/* cv::MorphTypes (the four built) and cv::MorphShapes */
+#define TBDK_MORPH_ERODE 0
+#define TBDK_MORPH_DILATE 1
+#define TBDK_MORPH_OPEN 2
+#define TBDK_MORPH_CLOSE 3
+#define TBDK_MORPH_RECT 0
+#define TBDK_MORPH_CROSS 1
+#define TBDK_MORPH_ELLIPSE 2
+
+/* cv::getStructuringElement (imgproc/src/morph.dispatch.cpp:135-186), host only: out gets
+ * kw x kh bytes, rows first, 1 = in.  CROSS uses the anchor, (-1, -1) is the centre; a 1 x 1
+ * element is a RECT; ELLIPSE rounds its half width half to even, in double.  TBDK_EINVAL: another
+ * shape, a size below 1, an anchor outside, out NULL. */
+int tbdk_structuring_element(int shape, int kw, int kh, int anchor_x, int anchor_y, uint8_t* out);
+
+/* cv::erode / cv::dilate / cv::morphologyEx(MORPH_OPEN, MORPH_CLOSE) on an 8-bit one-channel device
+ * image, 1..65535 a side, pitched, any alignment: per pixel the min (erode) or max (dilate) of the
+ * border-extended image over the element's non-zero positions, gray levels included.  OPEN is erode
+ * then dilate, CLOSE the reverse, each with the full `iterations`.  src == dst is allowed.
+ *   element  : host, kw x kh bytes, non-zero = in, read before the call returns; NULL: the
+ *              reference's 3 x 3 rectangle (kw, kh ignored)
+ *   anchor   : inside the element, or (-1, -1) for its centre
+ *   iterations, as morphOp (:952-972) applies them: 0, or a 1 x 1 element, copies src to dst; a NULL
+ *              element is one pass of the (1 + 2 it)-square rectangle anchored at (it, it); an
+ *              element without a zero and it > 1 is one pass of the k + (it - 1)(k - 1) rectangle
+ *              with the anchor times it, whatever the border (with an explicit border value this
+ *              differs from iterating; the reference's result is the one returned); any other
+ *              element runs it passes, each on the previous result
+ *   border_type  : TBDK_BORDER_CONSTANT, _REPLICATE, _REFLECT or _REFLECT_101, for images smaller
+ *              than the element too
+ *   border_value : -1 for morphologyDefaultBorderValue (under BORDER_CONSTANT the outside is
+ *              ignored), or 0..255, what a pixel outside counts as under BORDER_CONSTANT
+ * A rectangle runs as a row pass then a column pass, any other element as one 2-D pass per
+ * iteration; the element travels in the kernel arguments.  Enqueues its kernels on `stream` and
+ * returns: no upload, no host synchronisation, and no allocation unless the context's intermediate
+ * planes (up to two, width x height bytes each; calls on one context are ordered by the caller) have
+ * to grow.  TBDK_EINVAL, with nothing enqueued and dst untouched: a null image, an op other than
+ * the four (GRADIENT, TOPHAT, BLACKHAT and HITMISS are not built), a size outside 1..65535, a pitch
+ * below a row, BORDER_WRAP or any other border, a border value outside -1..255, negative
+ * iterations, an anchor outside, an element with no non-zero entry, an effective element (after the
+ * rules above) of more than 31 a side, more than 64 passes.  Timed as "morph". */
+int tbdk_morph_u8(tbdk_ctx* ctx, int op, const uint8_t* src, int width, int height, int src_pitch, uint8_t* dst,
+                  int dst_pitch, const uint8_t* element, int kw, int kh, int anchor_x, int anchor_y, int iterations,
+                  int border_type, int border_value, void* stream);
+
+/* cv::ConnectedComponentsAlgorithmsTypes and the columns of a stats row */
+#define TBDK_CCL_WU 0
+#define TBDK_CCL_DEFAULT (-1)
+#define TBDK_CCL_GRANA 1
+#define TBDK_CC_STAT_LEFT 0
+#define TBDK_CC_STAT_TOP 1
+#define TBDK_CC_STAT_WIDTH 2
+#define TBDK_CC_STAT_HEIGHT 3
+#define TBDK_CC_STAT_AREA 4
+
+/* cv::connectedComponentsWithStats (imgproc/src/connectedcomponents.cpp), ltype CV_32S, everything
+ * on the device.  img: 8-bit, width x height (width * height < 2^31), pitch in bytes; every non-zero
+ * pixel is foreground.  labels: int32, labels_pitch bytes a row (a multiple of 4), always complete:
+ * 0 for background, 1..N-1 for the components, numbered as the reference numbers them, by the raster
+ * position of a component's first pixel (TBDK_CCL_WU, and connectivity 4 whatever the type) or of
+ * its first 2 x 2 block (TBDK_CCL_GRANA / TBDK_CCL_DEFAULT at connectivity 8).  n_labels (device
+ * int32) gets N, the reference's return value.  stats (int32 [cap][5]: LEFT, TOP, WIDTH, HEIGHT,
+ * AREA) and centroids (double [cap][2]: double(sum x) / double(area) from 64-bit sums), either may be
+ * NULL: rows l < min(N, cap) are written, label 0's too, rows from N on are left untouched.  An
+ * image with no background pixel gives row 0 as the reference leaves it: INT_MAX, INT_MAX, the
+ * wrapped extents 2, 2, area 0 and a NaN centroid.  Enqueues seven to nine kernels on `stream` and
+ * returns: no host synchronisation, and no allocation unless the context's scratch (8 to 9 bytes a
+ * pixel plus 40 a stats row; calls on one context are ordered by the caller) has to grow.
+ * TBDK_EINVAL, nothing enqueued: a null img, labels or n_labels, a size below 1 or of 2^31 pixels
+ * or more, a pitch below a row, a labels pointer or pitch that is no multiple of 4, a connectivity
+ * other than 4 or 8, another ccltype, cap < 0, or cap < 1 with stats or centroids given.  Timed as
+ * "cc". */
+int tbdk_connected_components(tbdk_ctx* ctx, const uint8_t* img, int width, int height, int pitch, int32_t* labels,
+                              int labels_pitch, int connectivity, int ccltype, int32_t* stats, double* centroids,
+                              int cap, int32_t* n_labels, void* stream);
 
 /* ---- synthetic sequences (bench / test input) ----------------------------- */
 

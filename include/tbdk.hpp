@@ -1127,6 +1127,95 @@ inline std::unique_ptr<BackgroundSubtractorMOG2> createBackgroundSubtractorMOG2(
     return std::unique_ptr<BackgroundSubtractorMOG2>(new BackgroundSubtractorMOG2(ctx, history, varThreshold, detectShadows));
 }
 
+// ---- morphology and connected components (imgproc/src/morph.dispatch.cpp, connectedcomponents.cpp) over
+// tbdk_morph_u8 / tbdk_connected_components: 8-bit one-channel device images in, everything out stays on the
+// device, nothing synchronises.  Results are the CPU reference's bit for bit, label numbering included.
+enum MorphTypes { MORPH_ERODE = 0, MORPH_DILATE = 1, MORPH_OPEN = 2, MORPH_CLOSE = 3 };
+enum MorphShapes { MORPH_RECT = 0, MORPH_CROSS = 1, MORPH_ELLIPSE = 2 };
+enum ConnectedComponentsAlgorithmsTypes { CCL_WU = 0, CCL_DEFAULT = -1, CCL_GRANA = 1 };
+enum ConnectedComponentsTypes { CC_STAT_LEFT = 0, CC_STAT_TOP = 1, CC_STAT_WIDTH = 2, CC_STAT_HEIGHT = 3, CC_STAT_AREA = 4 };
+constexpr int MORPH_DEFAULT_BORDER_VALUE = -1;  // cv::morphologyDefaultBorderValue()
+
+struct Point {
+    int x = -1, y = -1;
+};
+
+// A host structuring element (a cv::Mat of CV_8U): rows first, non-zero = in.  Empty: the reference's empty
+// Mat, the 3 x 3 rectangle.
+struct StructuringElement {
+    int width = 0, height = 0;
+    std::vector<uint8_t> data;
+    bool empty() const { return data.empty(); }
+};
+
+// cv::getStructuringElement(shape, ksize, anchor)
+inline StructuringElement getStructuringElement(int shape, Size ksize, Point anchor = Point())
+{
+    StructuringElement e;
+    if (ksize.width < 1 || ksize.height < 1) throw Error(TBDK_EINVAL, "getStructuringElement");
+    e.width = ksize.width, e.height = ksize.height;
+    e.data.resize((size_t)ksize.width * ksize.height);
+    check(tbdk_structuring_element(shape, ksize.width, ksize.height, anchor.x, anchor.y, e.data.data()),
+          "tbdk_structuring_element");
+    return e;
+}
+
+// cv::morphologyEx(src, dst, op, kernel, anchor, iterations, borderType, borderValue), MORPH_ERODE / DILATE /
+// OPEN / CLOSE; dst may be src.  borderValue: MORPH_DEFAULT_BORDER_VALUE or 0..255
+inline void morphologyEx(Context& ctx, const GpuImage& src, const GpuImage& dst, int op, const StructuringElement& kernel,
+                         Point anchor = Point(), int iterations = 1, int borderType = TBDK_BORDER_CONSTANT,
+                         int borderValue = MORPH_DEFAULT_BORDER_VALUE, void* stream = nullptr)
+{
+    if (src.width != dst.width || src.height != dst.height) throw Error(TBDK_EINVAL, "morphologyEx: dst must have src's size");
+    check(tbdk_morph_u8(ctx.get(), op, src.data, src.width, src.height, src.pitch, dst.data, dst.pitch,
+                        kernel.empty() ? nullptr : kernel.data.data(), kernel.width, kernel.height, anchor.x, anchor.y,
+                        iterations, borderType, borderValue, stream),
+          "tbdk_morph_u8");
+}
+// cv::erode / cv::dilate
+inline void erode(Context& ctx, const GpuImage& src, const GpuImage& dst, const StructuringElement& kernel,
+                  Point anchor = Point(), int iterations = 1, int borderType = TBDK_BORDER_CONSTANT,
+                  int borderValue = MORPH_DEFAULT_BORDER_VALUE, void* stream = nullptr)
+{
+    morphologyEx(ctx, src, dst, MORPH_ERODE, kernel, anchor, iterations, borderType, borderValue, stream);
+}
+inline void dilate(Context& ctx, const GpuImage& src, const GpuImage& dst, const StructuringElement& kernel,
+                   Point anchor = Point(), int iterations = 1, int borderType = TBDK_BORDER_CONSTANT,
+                   int borderValue = MORPH_DEFAULT_BORDER_VALUE, void* stream = nullptr)
+{
+    morphologyEx(ctx, src, dst, MORPH_DILATE, kernel, anchor, iterations, borderType, borderValue, stream);
+}
+
+// The CV_32S label image of connectedComponents: device int32, pitch in bytes (a multiple of 4)
+struct GpuLabels {
+    int32_t* data = nullptr;
+    int width = 0, height = 0, pitch = 0;
+};
+
+// cv::connectedComponents(image, labels, connectivity, CV_32S, ccltype): nLabels (device int32) gets the
+// return value N, with no host synchronisation
+inline void connectedComponents(Context& ctx, const GpuImage& image, const GpuLabels& labels, int32_t* nLabels,
+                                int connectivity = 8, int ccltype = CCL_DEFAULT, void* stream = nullptr)
+{
+    if (image.width != labels.width || image.height != labels.height)
+        throw Error(TBDK_EINVAL, "connectedComponents: labels must have the image's size");
+    check(tbdk_connected_components(ctx.get(), image.data, image.width, image.height, image.pitch, labels.data,
+                                    labels.pitch, connectivity, ccltype, nullptr, nullptr, 0, nLabels, stream),
+          "tbdk_connected_components");
+}
+// cv::connectedComponentsWithStats: stats (device int32 [maxLabels][5], CC_STAT_*) and centroids (device double
+// [maxLabels][2]) get the rows below min(N, maxLabels), row 0 the background's; the rest stays as it was
+inline void connectedComponentsWithStats(Context& ctx, const GpuImage& image, const GpuLabels& labels, int32_t* stats,
+                                         double* centroids, int maxLabels, int32_t* nLabels, int connectivity = 8,
+                                         int ccltype = CCL_DEFAULT, void* stream = nullptr)
+{
+    if (image.width != labels.width || image.height != labels.height)
+        throw Error(TBDK_EINVAL, "connectedComponentsWithStats: labels must have the image's size");
+    check(tbdk_connected_components(ctx.get(), image.data, image.width, image.height, image.pitch, labels.data,
+                                    labels.pitch, connectivity, ccltype, stats, centroids, maxLabels, nLabels, stream),
+          "tbdk_connected_components");
+}
+
 // The sample's whole per-frame path (samples/gpu/tbd.cpp:568-622) on a TbdLoop:
 // colour frame -> cvtColor -> optional resize -> HOG detectMultiScale -> the
 // loop (tbdk_tbd_step_image).  `loop` and `ctx` must outlive it.

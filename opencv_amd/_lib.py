@@ -339,6 +339,14 @@ SIGNATURES = {
     "tbdk_mog2_get_background": (C.c_int, [C.c_void_p, C.c_void_p, C.c_int, C.c_void_p]),
     "tbdk_mog2_get_model": (C.c_int, [C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p]),
     "tbdk_mog2_frames": (C.c_int, [C.c_void_p, C.POINTER(C.c_int)]),
+    "tbdk_structuring_element": (C.c_int, [C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, C.c_void_p]),
+    # ctx, op, src, w, h, spitch, dst, dpitch, element, kw, kh, ax, ay, iterations, border, border value, stream
+    "tbdk_morph_u8": (C.c_int, [C.c_void_p, C.c_int, C.c_void_p, C.c_int, C.c_int, C.c_int, C.c_void_p, C.c_int,
+                                C.c_void_p, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, C.c_void_p]),
+    # ctx, img, w, h, pitch, labels, labels pitch, connectivity, ccltype, stats, centroids, cap, n_labels, stream
+    "tbdk_connected_components": (C.c_int, [C.c_void_p, C.c_void_p, C.c_int, C.c_int, C.c_int, C.c_void_p, C.c_int,
+                                            C.c_int, C.c_int, C.c_void_p, C.c_void_p, C.c_int, C.c_void_p,
+                                            C.c_void_p]),
     "tbdk_box_propagate": (C.c_int, [C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_int,
                                      C.c_int, C.c_void_p, C.c_void_p]),
     "tbdk_ransac_default_params": (C.c_int, [C.POINTER(RansacParams)]),

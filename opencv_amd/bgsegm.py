@@ -3,6 +3,8 @@
   * BackgroundSubtractorMOG2 <- cv::BackgroundSubtractorMOG2 / cv::cuda::BackgroundSubtractorMOG2
         (modules/video/include/opencv2/video/background_segm.hpp:90-219,
          impl modules/video/src/bgfg_gaussmix2.cpp)
+  * detections_from_stats: the stats rows of imgproc.connected_components_with_stats on a cleaned mask as the
+        detections TbdLoop.step takes (samples/cpp/segment_objects.cpp's refineSegments, with boxes out)
 
 Numerics are the CPU implementation's, bit for bit (mask, background image and
 model).  Frames are uint8 or float32 torch tensors on the HIP device, H x W or
@@ -18,6 +20,7 @@ from __future__ import annotations
 
 import ctypes as C
 
+import numpy as np
 import torch
 
 from . import _lib
@@ -192,3 +195,26 @@ def createBackgroundSubtractorMOG2(history: int = 500, varThreshold: float = 16,
                                    ctx: Context | None = None) -> BackgroundSubtractorMOG2:
     """cv::createBackgroundSubtractorMOG2 (bgfg_gaussmix2.cpp:958-962)"""
     return BackgroundSubtractorMOG2(history, varThreshold, detectShadows, ctx=ctx)
+
+
+def detections_from_stats(stats: torch.Tensor, n_labels, min_area: int = 1, max_area: int | None = None) -> np.ndarray:
+    """The components of imgproc.connected_components_with_stats as detections for tbd.TbdLoop.step: a
+    tbd.DET_DTYPE array with id = label, the box LEFT / TOP / WIDTH / HEIGHT and confidence 1.0, label 0 (the
+    background) and the components whose area lies outside min_area..max_area left out.  Copies the
+    min(N, rows of stats) stats rows to the host, which waits for the current stream: the one transfer of
+    the mask -> boxes chain."""
+    from .tbd import DET_DTYPE
+
+    n = int(n_labels.reshape(-1)[0].item()) if isinstance(n_labels, torch.Tensor) else int(n_labels)
+    rows = stats[:max(0, min(n, stats.shape[0]))].cpu().numpy()
+    rows = rows[1:]
+    labels = np.arange(1, len(rows) + 1, dtype=np.int32)
+    keep = rows[:, 4] >= min_area
+    if max_area is not None:
+        keep &= rows[:, 4] <= max_area
+    rows, labels = rows[keep], labels[keep]
+    out = np.zeros(len(rows), DET_DTYPE)
+    out["id"] = labels
+    out["x"], out["y"], out["width"], out["height"] = rows[:, 0], rows[:, 1], rows[:, 2], rows[:, 3]
+    out["confidence"] = 1.0
+    return out

@@ -167,6 +167,8 @@ int tbdk_ctx_destroy(tbdk_ctx* ctx)
     front_release(ctx);
     if (ctx->dense_buf) (void)hipFree(ctx->dense_buf);
     if (ctx->dcase_buf) (void)hipFree(ctx->dcase_buf);
+    if (ctx->morph_buf) (void)hipFree(ctx->morph_buf);
+    if (ctx->cc_buf) (void)hipFree(ctx->cc_buf);
     for (hipStream_t st : {ctx->tbd_side, ctx->tbd_la, ctx->tbd_early})
         if (st) (void)hipStreamDestroy(st);
     delete ctx;
@@ -365,6 +367,14 @@ int tbdk_ctx_debug_fill_scratch(tbdk_ctx* ctx, int byte, int64_t* bytes_filled)
     if (e == hipSuccess && ctx->dcase_buf) {
         e = hipMemset(ctx->dcase_buf, byte, ctx->dcase_cap);
         n += (int64_t)ctx->dcase_cap;
+    }
+    if (e == hipSuccess && ctx->morph_buf) {
+        e = hipMemset(ctx->morph_buf, byte, ctx->morph_cap);
+        n += (int64_t)ctx->morph_cap;
+    }
+    if (e == hipSuccess && ctx->cc_buf) {
+        e = hipMemset(ctx->cc_buf, byte, ctx->cc_cap);
+        n += (int64_t)ctx->cc_cap;
     }
     if (e == hipSuccess) e = hipDeviceSynchronize();
     if (bytes_filled) *bytes_filled = n;

@@ -142,6 +142,10 @@ struct tbdk_ctx {
     std::mutex tbd_mu;
     hipStream_t tbd_side = nullptr, tbd_la = nullptr, tbd_early = nullptr;
     tbdk::FrontScratch* front = nullptr;  // resize coefficient tables by size (frontend.hip)
+    void* morph_buf = nullptr;  // tbdk_morph_u8's intermediate planes (morph.hip), grown on demand
+    size_t morph_cap = 0;       // bytes
+    void* cc_buf = nullptr;     // tbdk_connected_components' parent, key and rank planes, tile sums, stats sums (ccl.hip)
+    size_t cc_cap = 0;          // bytes
 };
 
 namespace tbdk {

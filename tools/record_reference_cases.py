@@ -7,7 +7,9 @@ goodFeaturesToTrack on CV_32F images: tests/_gftt_f32_cases.py; cornerSubPix:
 tests/_subpix_cases.py; goodFeaturesToTrack on whole frames:
 tests/_gftt_frame_cases.py; remap and warpPerspective: tests/_remap_cases.py;
 findHomography: tests/_homography_cases.py; estimateAffine2D and
-estimateAffinePartial2D: tests/_affine2d_cases.py)
+estimateAffinePartial2D: tests/_affine2d_cases.py; erode, dilate and
+morphologyEx: tests/_morph_cases.py; connectedComponentsWithStats:
+tests/_cc_cases.py)
 into tests/golden/reference_<op>.npz, through tools/reference_driver.cpp (how to
 build it: tools/record_reference_cases.md).
 
@@ -18,8 +20,8 @@ runtime dispatch) and `noavx2` (OPENCV_CPU_DISABLE=AVX2,AVX512_SKX in the
 child's environment only).  The driver prints checkHardwareSupport; a run whose
 flags do not show the intended state is an error, so a host without AVX2 cannot
 record.  Where the two recordings are byte-identical one copy is stored
-(state "both"); this is asserted for the pyramid, PyrLK, warpAffine, remap and
-warpPerspective.  Where
+(state "both"); this is asserted for the pyramid, PyrLK, warpAffine, remap,
+warpPerspective, morph and cc.  Where
 they differ, the state the oracle models is stored in full, and for the other
 one: whether the integer-valued results were equal (and those results where
 they were not), the share of equal 32-bit words and the largest absolute
@@ -50,6 +52,8 @@ import _remap_cases as PC  # noqa: E402
 import _homography_cases as HC  # noqa: E402
 import _affine2d_cases as AC  # noqa: E402
 import _mog2_cases as GC  # noqa: E402
+import _morph_cases as BC  # noqa: E402
+import _cc_cases as LC  # noqa: E402
 
 LIMIT = 256 * 1024
 STATES = ("default", "noavx2")
@@ -57,7 +61,8 @@ STATES = ("default", "noavx2")
 MODELLED = {"pyramid": "both", "pyrlk": "both", "warpaffine": "both", "gftt": "noavx2", "gftt_mask": "noavx2",
             "cornermaps": "noavx2", "gftt_f32": "noavx2", "subpix": "both", "gftt_frame": "noavx2",
             "circle": "both", "remap": "both", "warpperspective": "both", "farneback": "noavx2",
-            "farneback_box": "noavx2", "hog": "default", "homography": "noavx2", "affine2d": "noavx2", "mog2": "both"}
+            "farneback_box": "noavx2", "hog": "default", "homography": "noavx2", "affine2d": "noavx2", "mog2": "both",
+            "morph": "both", "cc": "both"}
 
 
 class Driver:
@@ -426,6 +431,46 @@ def rec_mog2(d):
     return cases, {}
 
 
+def rec_morph(d):
+    """erode / dilate / morphologyEx on the cases of tests/_morph_cases.py, and the getStructuringElement table
+    (bit-packed).  The CROSS and ELLIPSE elements the cases use are checked against the reference's own"""
+    extra = {}
+    for k, (shape, kw, kh, anchor) in enumerate(BC.strel_cases()):
+        _, rd = d.run("strel", {}, shape=shape, kw=kw, kh=kh, ax=anchor[0], ay=anchor[1])
+        e = rd("e", np.uint8).reshape(kh, kw)
+        assert np.isin(e, (0, 1)).all()
+        extra[f"strel_{k}"] = np.packbits(e)
+    elems = BC.elements()
+    for name, (shape, kw, kh, anchor) in BC.shaped().items():
+        _, rd = d.run("strel", {}, shape=shape, kw=kw, kh=kh, ax=anchor[0], ay=anchor[1])
+        assert np.array_equal(rd("e", np.uint8).reshape(kh, kw), elems[name]), name
+    cases = []
+    for c in BC.cases():
+        img, e = BC.image(c["w"], c["h"], c["content"]), elems[c["elem"]]
+        files, kw = dict(a=img), {}
+        if e is not None:
+            files["elem"] = e
+            kw = dict(kw=e.shape[1], kh=e.shape[0])
+        _, rd = d.run("morph", files, w=c["w"], h=c["h"], mop=c["op"], ax=c["anchor"][0], ay=c["anchor"][1],
+                      it=c["it"], border=c["border"], bval=c["bval"], inplace=int(c["inplace"]), **kw)
+        cases.append((dict(d=rd("d", np.uint8).reshape(c["h"], c["w"])), {}))
+    return cases, extra
+
+
+def rec_cc(d):
+    """connectedComponentsWithStats on the cases of tests/_cc_cases.py: per case `s`, N rows of nine int32 (the
+    five stats, then the two centroids' 64-bit words, low half first: row 0 of an image without background is
+    0/0), always whole, and the labels whole or as row CRCs"""
+    cases = []
+    for content, w, h, conn, t in LC.cases():
+        out, rd = d.run("cc", dict(a=LC.image(content, w, h)), w=w, h=h, conn=conn, type=t)
+        n = int(out[0].split()[1])
+        ints = dict(labels=LC.stored_labels(rd("labels", np.int32).reshape(h, w)),
+                    s=LC.stored_stats(rd("stats", np.int32).reshape(n, 5), rd("cent", np.float64).reshape(n, 2)))
+        cases.append((ints, {}))
+    return cases, {}
+
+
 def rec_farneback(d, table=None):
     cases, meta = [], []
     for w, h, ps, pn, ws, flags, use_init in table or RC.FB_CASES:
@@ -527,12 +572,14 @@ RECORDERS = {"pyramid": rec_pyramid, "pyrlk": rec_pyrlk, "gftt": rec_gftt, "gftt
              "cornermaps": rec_cornermaps, "gftt_f32": rec_gftt_f32, "subpix": rec_subpix, "gftt_frame": rec_gftt_frame,
              "circle": rec_circle, "warpaffine": rec_warpaffine, "remap": rec_remap,
              "warpperspective": rec_warpperspective, "farneback": rec_farneback, "farneback_box": rec_farneback_box,
-             "hog": rec_hog, "homography": rec_homography, "affine2d": rec_affine2d, "mog2": rec_mog2}
+             "hog": rec_hog, "homography": rec_homography, "affine2d": rec_affine2d, "mog2": rec_mog2,
+             "morph": rec_morph, "cc": rec_cc}
 # bytes up to which an output is stored whole (tests/_reference_cases.py: WHOLE_LIMIT).  The kernels are
 # compared with the box Farneback flows within a tolerance, so all six stay whole (about 7 KB under LIMIT)
 WHOLE = {"farneback": 20480, "farneback_box": 72800, "pyrlk": 1 << 20, "gftt": 1 << 20, "gftt_mask": 1 << 20,
          "hog": 16384, "subpix": 1 << 20, "gftt_frame": 1 << 20, "remap": PC.WHOLE_LIMIT,
-         "warpperspective": PC.WHOLE_LIMIT, "homography": 1 << 20, "affine2d": 1 << 20, "mog2": 1 << 20}
+         "warpperspective": PC.WHOLE_LIMIT, "homography": 1 << 20, "affine2d": 1 << 20, "mog2": 1 << 20,
+         "morph": BC.WHOLE_LIMIT, "cc": 1 << 20}
 # (gftt_f32: maps above RC.WHOLE_LIMIT as row CRCs; its corner lists are far below it)
 
 
@@ -577,6 +624,10 @@ def case_label(op, i):
         return AC.label(i)
     if op == "mog2":
         return GC.label(i)
+    if op == "morph":
+        return BC.label(i)
+    if op == "cc":
+        return LC.label(i)
     if op == "circle":
         return "centre ({}, {}) radius {}".format(*KT.CIRCLE_CASES[i])
     if op == "cornermaps":

@@ -47,6 +47,15 @@
 //                                                  non-zero byte of bg=): createBackgroundSubtractorMOG2, every
 //                                                  setter, apply(frame, mask, rates[t]) per frame and
 //                                                  getBackgroundImage after the marked ones
+//   morph a= w= h= mop=0..3 [elem= kw= kh=] ax= ay= it= border= bval= inplace=0|1
+//                                                  -> d (u8): erode / dilate (mop 0 / 1) or morphologyEx (mop 2 / 3)
+//                                                  with the element (raw kw x kh bytes; absent: an empty Mat),
+//                                                  anchor, iterations, border type and border value (-1:
+//                                                  morphologyDefaultBorderValue()); inplace=1: dst is src
+//   cc    a= w= h= conn= type=                     -> labels (i32), stats (i32 x5), cent (f64 x2); prints "n N":
+//                                                  connectedComponentsWithStats(a, labels, stats, centroids, conn,
+//                                                  CV_32S, type)
+//   strel shape= kw= kh= ax= ay=                   -> e (u8, kw x kh): getStructuringElement (no input image)
 #include <cmath>
 #include <cstdio>
 #include <cstdlib>
@@ -271,8 +280,54 @@ static int run_mog2(const std::string& out)
     return 0;
 }
 
+// erode / dilate / morphologyEx, connectedComponentsWithStats, getStructuringElement
+static int run_blobs(const std::string& op, const std::string& out)
+{
+    if (op == "strel") {
+        Mat e = getStructuringElement(iarg("shape"), Size(iarg("kw"), iarg("kh")), Point(iarg("ax"), iarg("ay")));
+        if (e.type() != CV_8UC1) throw std::runtime_error("getStructuringElement: not CV_8UC1");
+        wr(out, "e", e);
+        return 0;
+    }
+    const int w = iarg("w"), h = iarg("h");
+    Mat a = image("a", w, h, 1);
+    if (op == "cc") {
+        Mat labels, stats, cent;
+        const int n = connectedComponentsWithStats(a, labels, stats, cent, iarg("conn"), CV_32S, iarg("type"));
+        if (labels.type() != CV_32SC1 || stats.type() != CV_32SC1 || cent.type() != CV_64FC1 || stats.rows != n ||
+            stats.cols != 5 || cent.rows != n || cent.cols != 2)
+            throw std::runtime_error("connectedComponentsWithStats: unexpected output layout");
+        std::printf("n %d\n", n);
+        wr(out, "labels", labels);
+        wr(out, "stats", stats);
+        wr(out, "cent", cent);
+        return 0;
+    }
+    Mat elem;
+    if (has("elem")) {
+        elem.create(iarg("kh"), iarg("kw"), CV_8UC1);
+        rd(arg("elem"), elem.data, (size_t)elem.rows * elem.cols);
+    }
+    const Point anchor(iarg("ax"), iarg("ay"));
+    const int mop = iarg("mop"), it = iarg("it"), border = iarg("border"), bval = iarg("bval");
+    const Scalar bv = bval < 0 ? morphologyDefaultBorderValue() : Scalar::all(bval);
+    Mat d;
+    if (iarg("inplace")) d = a;
+    const uchar* before = a.data;
+    if (mop == MORPH_ERODE)
+        erode(a, d, elem, anchor, it, border, bv);
+    else if (mop == MORPH_DILATE)
+        dilate(a, d, elem, anchor, it, border, bv);
+    else
+        morphologyEx(a, d, mop, elem, anchor, it, border, bv);
+    if (iarg("inplace") && d.data != before) throw std::runtime_error("the in-place call reallocated its image");
+    wr(out, "d", d);
+    return 0;
+}
+
 static int run(const std::string& op, const std::string& out)
 {
+    if (op == "morph" || op == "cc" || op == "strel") return run_blobs(op, out);
     if (op == "mog2") return run_mog2(out);
     if (op == "homography") return run_homography(out);
     if (op == "affine2d") return run_affine2d(out);
