@@ -314,7 +314,36 @@ int tbdk_timing_calls(tbdk_ctx* ctx, const char* name, int64_t* calls);
  *     pixel size.
  * A pitch below a row, or one that breaks these rules, is TBDK_EINVAL, and
  * nothing is enqueued.  Results do not depend on the layout.
- * tests/test_gpu_views_*.py check this contract entry point by entry point. */
+ * tests/test_gpu_views_*.py check this contract entry point by entry point.
+ *
+ * Extents.  A pitch is an int, so below 2^31 bytes, and nothing else bounds
+ * pitch * height: a small image with a huge pitch (a column crop of a large
+ * mosaic, one plane of a huge interleaved surface) is legal, its rows may span
+ * 2 GiB, 4 GiB and more, and every kernel forms row addresses in 64 bits.  The
+ * exception are the kernels that read the caller's memory through a buffer
+ * descriptor, whose sizes and row offsets are 32-bit unsigned (rebasing per row
+ * would cost registers on the loop's critical chain): the GFTT eigenvalue walk
+ * and PyrLK on a level 0 borrowed from the caller.  They return TBDK_EINVAL,
+ * with nothing enqueued, beyond these bounds (in bytes):
+ *   - tbdk_gftt_rois, _masked, _px: each ROI's rows may span at most 4294967295
+ *     bytes: (roi.height - 1) * pitch + roi.width * pixel bytes, and with a mask
+ *     (roi.height - 1) * mask_pitch + roi.width.  The bound is per ROI: a small
+ *     ROI may lie anywhere in a frame of any extent.
+ *   - tbdk_corner_min_eig_val, and tbdk_corner_response / _px with block_size 3
+ *     and no Harris (the same walk, over the whole image as one ROI):
+ *     (height - 1) * pitch + width * pixel bytes at most 4294967295.  The other
+ *     block sizes and Harris have no bound, and dst_pitch has none.
+ *   - tbdk_pyr_build_borrowed: pitch * height at most 4294967295 (and so
+ *     tbdk_lk_sparse / tbdk_lk_sparse_fb on that pyramid).
+ *   - tbdk_tbd_run: pitch * height at most 4294967295 (its GFTT launched ahead
+ *     reads the caller's next frame; with tbd_borrow_l0 PyrLK reads the frames).
+ *     tbdk_tbd_step, _step_ahead, _step_image and tbdk_klt_tracker_step copy the
+ *     frame into their own pyramid first and have no bound.
+ *   - tbdk_tbd_set_corner_mask: (height - 1) * mask_pitch + width at most
+ *     4294967295.
+ * tests/test_gpu_far_views.py runs every pitch-taking entry point on views that
+ * span 2^31 and 2^32 bytes, and each bound at its last accepted and first
+ * rejected pitch. */
 
 /* ---- pyramids ------------------------------------------------------------ */
 

@@ -352,7 +352,7 @@ extern "C" int tbdk_connected_components(tbdk_ctx* ctx, const uint8_t* img, int 
 {
     if (!ctx || !img || !labels || !n_labels) return TBDK_EINVAL;
     if (width < 1 || height < 1 || (int64_t)width * height >= ((int64_t)1 << 31) || pitch < width) return TBDK_EINVAL;
-    if (labels_pitch < width * 4 || (labels_pitch & 3) != 0 || (reinterpret_cast<uintptr_t>(labels) & 3) != 0)
+    if (labels_pitch < (int64_t)width * 4 || (labels_pitch & 3) != 0 || (reinterpret_cast<uintptr_t>(labels) & 3) != 0)
         return TBDK_EINVAL;
     if (connectivity != 4 && connectivity != 8) return TBDK_EINVAL;
     if (ccltype != TBDK_CCL_DEFAULT && ccltype != TBDK_CCL_WU && ccltype != TBDK_CCL_GRANA) return TBDK_EINVAL;

@@ -1323,7 +1323,7 @@ int tbdk_farneback(tbdk_ctx* ctx, const uint8_t* prev, const uint8_t* next, int 
                    float* flow, int flow_pitch, const tbdk_farneback_params* p, void* stream)
 {
     if (!ctx || !prev || !next || !flow || width <= 0 || height <= 0 || pitch < width) return TBDK_EINVAL;
-    if (flow_pitch < 8 * width || flow_pitch % 8 != 0) return TBDK_EINVAL;
+    if (flow_pitch < (int64_t)8 * width || flow_pitch % 8 != 0) return TBDK_EINVAL;
     int rc = fb_check(p);
     if (rc != TBDK_OK) return rc;
     int nl = 0;
@@ -1520,7 +1520,7 @@ int tbdk_fb_level_image(tbdk_ctx* ctx, const uint8_t* img, int width, int height
                         int dst_height, int smooth_size, double sigma, float* dst, int dst_pitch, void* stream)
 {
     if (!ctx || !img || !dst || width <= 0 || height <= 0 || pitch < width || dst_width <= 0 || dst_height <= 0 ||
-        dst_pitch < 4 * dst_width || dst_pitch % 4 != 0)
+        dst_pitch < (int64_t)4 * dst_width || dst_pitch % 4 != 0)
         return TBDK_EINVAL;
     LevelImagePlan plan;
     int rc = plan_level_image(width, height, dst_width, dst_height, smooth_size, sigma, &plan);
@@ -1542,8 +1542,8 @@ int tbdk_fb_level_image(tbdk_ctx* ctx, const uint8_t* img, int width, int height
 int tbdk_fb_poly_exp(tbdk_ctx* ctx, const float* src, int width, int height, int src_pitch, int poly_n,
                      double poly_sigma, float* dst, int dst_pitch, void* stream)
 {
-    if (!ctx || !src || !dst || width <= 0 || height <= 0 || src_pitch < 4 * width || src_pitch % 4 != 0 ||
-        dst_pitch < 4 * width || dst_pitch % 4 != 0 || poly_n < 1 || poly_n > kFbMaxPolyN)
+    if (!ctx || !src || !dst || width <= 0 || height <= 0 || src_pitch < (int64_t)4 * width || src_pitch % 4 != 0 ||
+        dst_pitch < (int64_t)4 * width || dst_pitch % 4 != 0 || poly_n < 1 || poly_n > kFbMaxPolyN)
         return TBDK_EINVAL;
     DeviceGuard g(ctx->device);
     hipStream_t s = static_cast<hipStream_t>(stream);

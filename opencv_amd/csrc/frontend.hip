@@ -408,7 +408,7 @@ int front_cvt_color(tbdk_ctx* ctx, const uint8_t* src, int width, int height, in
     else if (code == TBDK_COLOR_BGR2BGRA) scn = 3, dcn = 4;
     else if (code == TBDK_COLOR_GRAY2BGR) scn = 1, dcn = 3;
     else return TBDK_EINVAL;
-    if (src_pitch < width * scn || dst_pitch < width * dcn) return TBDK_EINVAL;
+    if (src_pitch < (int64_t)width * scn || dst_pitch < (int64_t)width * dcn) return TBDK_EINVAL;
     if (overlaps(src, height, src_pitch, width * scn, dst, height, dst_pitch, width * dcn)) return TBDK_EINVAL;
     const dim3 grid = row_grid(width, height), block(256);
     const int rec = timing_begin(ctx, "cvt_color", s);
@@ -439,7 +439,7 @@ static int front_resize_impl(tbdk_ctx* ctx, const uint8_t* src, int width, int h
     } else if (cn != 1 && cn != 3 && cn != 4) {
         return TBDK_EINVAL;
     }
-    if (src_pitch < width * cn || dst_pitch < dst_width * dcn) return TBDK_EINVAL;
+    if (src_pitch < (int64_t)width * cn || dst_pitch < (int64_t)dst_width * dcn) return TBDK_EINVAL;
     if (overlaps(src, height, src_pitch, width * cn, dst, dst_height, dst_pitch, dst_width * dcn)) return TBDK_EINVAL;
     if (dst_width == width && dst_height == height) {  // the reference copies
         if (code >= 0) return front_cvt_color(ctx, src, width, height, src_pitch, dst, dst_pitch, code, s);

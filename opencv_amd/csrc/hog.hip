@@ -1109,7 +1109,7 @@ static int group_and_clip(std::vector<int>& r, std::vector<double>& wt, int thr,
 static int prepare(tbdk_ctx* ctx, const uint8_t* img, int w, int h, int pitch, int cn, const tbdk_hog_params* p,
                    const float* svm, int svm_len, HogPlan& pl, int64_t hit_cap, hipStream_t s)
 {
-    if (!ctx || !img || !svm || w <= 0 || h <= 0 || (cn != 1 && cn != 3 && cn != 4) || pitch < w * cn)
+    if (!ctx || !img || !svm || w <= 0 || h <= 0 || (cn != 1 && cn != 3 && cn != 4) || pitch < (int64_t)w * cn)
         return TBDK_EINVAL;
     int rc = hog_check(p);
     if (rc != TBDK_OK) return rc;
@@ -1290,7 +1290,7 @@ int tbdk_hog_resize(tbdk_ctx* ctx, const uint8_t* src, int width, int height, in
                     int dst_width, int dst_height, int dst_pitch, void* stream)
 {
     if (!ctx || !src || !dst || width <= 0 || height <= 0 || dst_width <= 0 || dst_height <= 0 || cn < 1 || cn > 4 ||
-        pitch < width * cn || dst_pitch < dst_width * cn)
+        pitch < (int64_t)width * cn || dst_pitch < (int64_t)dst_width * cn)
         return TBDK_EINVAL;
     DeviceGuard g(ctx->device);
     const ExactAxis ax = exact_axis(width, dst_width), ay = exact_axis(height, dst_height);
@@ -1305,7 +1305,8 @@ int tbdk_hog_gradient(tbdk_ctx* ctx, const uint8_t* img, int width, int height, 
                       int qangle_pitch, void* stream)
 {
     if (!ctx || !img || !grad || !qangle || width <= 0 || height <= 0 || (cn != 1 && cn != 3 && cn != 4) ||
-        pitch < width * cn || grad_pitch < 8 * width || grad_pitch % 8 || qangle_pitch < 2 * width ||
+        pitch < (int64_t)width * cn || grad_pitch < (int64_t)8 * width || grad_pitch % 8 ||
+        qangle_pitch < (int64_t)2 * width ||
         qangle_pitch % 2)
         return TBDK_EINVAL;
     if (hog_check(params) != TBDK_OK) return TBDK_EINVAL;
@@ -1317,8 +1318,8 @@ int tbdk_hog_gradient(tbdk_ctx* ctx, const uint8_t* img, int width, int height, 
 int tbdk_hog_blocks(tbdk_ctx* ctx, const float* grad, int grad_pitch, const uint8_t* qangle, int qangle_pitch,
                     int width, int height, const tbdk_hog_params* params, float* blocks, void* stream)
 {
-    if (!ctx || !grad || !qangle || !blocks || grad_pitch % 8 || grad_pitch < 8 * width || qangle_pitch % 2 ||
-        qangle_pitch < 2 * width)
+    if (!ctx || !grad || !qangle || !blocks || grad_pitch % 8 || grad_pitch < (int64_t)8 * width || qangle_pitch % 2 ||
+        qangle_pitch < (int64_t)2 * width)
         return TBDK_EINVAL;
     if (hog_check(params) != TBDK_OK) return TBDK_EINVAL;
     if (width < params->block_w || height < params->block_h) return TBDK_EINVAL;

@@ -115,7 +115,7 @@ int tbdk_lk_dense(tbdk_ctx* ctx, const tbdk_pyr* prev, const tbdk_pyr* next, flo
     prm.flags &= ~TBDK_OPTFLOW_USE_INITIAL_FLOW;
     const int w = prev->lv[0].width, h = prev->lv[0].height;
     if (next->nlevels <= 0 || next->lv[0].width != w || next->lv[0].height != h) return TBDK_EINVAL;
-    if (flow_pitch < 8 * w || flow_pitch % 8 != 0 || (status && status_pitch < w)) return TBDK_EINVAL;
+    if (flow_pitch < (int64_t)8 * w || flow_pitch % 8 != 0 || (status && status_pitch < w)) return TBDK_EINVAL;
     const int64_t n = (int64_t)w * h;
     if (n > INT32_MAX) return TBDK_EINVAL;
     DeviceGuard g(ctx->device);

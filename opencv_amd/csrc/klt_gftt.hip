@@ -156,6 +156,11 @@ struct EigLane {
 // byte.  Only output lanes read (they hold their own column, never a mirrored
 // one); every other lane's offset lies past the buffer, which loads 0, so halo
 // and reflected lanes never count toward the masked maximum.
+// The byte offset of ROI row `row` in a caller's image or mask, as the 32-bit
+// unsigned offset a buffer load takes: exact while the ROI's rows span at most
+// 2^32 - 1 bytes, which the entry points check (kGfttMaxSpan, tbdk.h "image layout")
+__device__ __forceinline__ uint32_t row_off(int row, int pitch) { return (uint32_t)row * (uint32_t)pitch; }
+
 struct EigMask {
     __amdgpu_buffer_rsrc_t rs;
     uint32_t col;  // the lane's byte offset in a mask row, or past the buffer
@@ -163,7 +168,7 @@ struct EigMask {
 };
 __device__ __forceinline__ bool eig_mask_ld(const EigMask& m, int row)
 {
-    return __builtin_amdgcn_raw_buffer_load_b8(m.rs, m.col, row * m.pitch, 0) != 0;
+    return __builtin_amdgcn_raw_buffer_load_b8(m.rs, m.col, (int)row_off(row, m.pitch), 0) != 0;
 }
 
 // PX: the image's pixel type (TBDK_PIX_*); the lane's one load of a row is of
@@ -172,11 +177,11 @@ template <int PX = TBDK_PIX_U8>
 __device__ __forceinline__ float eig_ld(const EigLane& g, int row)
 {
     if constexpr (PX == TBDK_PIX_F32)
-        return __uint_as_float(__builtin_amdgcn_raw_buffer_load_b32(g.rs, g.x * 4, row * g.pitch, 0));
+        return __uint_as_float(__builtin_amdgcn_raw_buffer_load_b32(g.rs, g.x * 4, (int)row_off(row, g.pitch), 0));
     else if constexpr (PX == TBDK_PIX_U16)
-        return (float)__builtin_amdgcn_raw_buffer_load_b16(g.rs, g.x * 2, row * g.pitch, 0);
+        return (float)__builtin_amdgcn_raw_buffer_load_b16(g.rs, g.x * 2, (int)row_off(row, g.pitch), 0);
     else
-        return (float)__builtin_amdgcn_raw_buffer_load_b8(g.rs, g.x, row * g.pitch, 0);
+        return (float)__builtin_amdgcn_raw_buffer_load_b8(g.rs, g.x, (int)row_off(row, g.pitch), 0);
 }
 
 // Sobel row terms of the pixel row whose own value is v (neighbours by DPP).
@@ -393,16 +398,18 @@ __device__ __forceinline__ void gftt_eig_body(const GfttArgs& a)
     g.H = H;
     g.hm2 = H >= 2 ? H - 2 : 0;
     g.pitch = a.pitch;
-    // the ROI's rows as one buffer (every lane loads a column inside the ROI);
-    // for the wider pixels its last row ends with the ROI's
+    // the ROI's rows as one buffer (every lane loads a column inside the ROI); its
+    // last row ends with the ROI's.  The size is the descriptor's 32-bit unsigned
+    // record count: the entry points reject a ROI whose rows span more
     g.rs = __builtin_amdgcn_make_buffer_rsrc(const_cast<uint8_t*>(a.img + (size_t)R.y * a.pitch + (size_t)R.x * kBpp),
-                                             (short)0, PX == TBDK_PIX_U8 ? a.pitch * H : a.pitch * (H - 1) + R.w * kBpp,
+                                             (short)0, (int)(row_off(H - 1, a.pitch) + (uint32_t)(R.w * kBpp)),
                                              0x00020000);
     EigMask gm{};
     if constexpr (masked) {  // rows a.mask_pitch apart; the last row ends with the ROI
         gm.rs = __builtin_amdgcn_make_buffer_rsrc(const_cast<uint8_t*>(a.mask + (size_t)R.y * a.mask_pitch + R.x),
-                                                  (short)0, a.mask_pitch * (H - 1) + R.w, 0x00020000);
-        gm.col = g.out_lane ? (uint32_t)g.x : 0x80000000u;
+                                                  (short)0, (int)(row_off(H - 1, a.mask_pitch) + (uint32_t)R.w),
+                                                  0x00020000);
+        gm.col = g.out_lane ? (uint32_t)g.x : 0xFFFFFFFFu;  // past a buffer of any accepted size (< 2^32 bytes)
         gm.pitch = a.mask_pitch;
     }
     float* E = a.eig + R.off + g.x;

@@ -168,9 +168,11 @@
         const int hp = L.h + 2 * L.ipad;
         // an unpadded level (pad 0: the TBD loop's level 0, the frame itself) is
         // bounded exactly; padded levels carry 256 bytes of over-read room
-        const __amdgpu_buffer_rsrc_t rI = make_rsrc(L.I, L.ipitch * hp + (L.ipad ? 256 : 0));
-        const __amdgpu_buffer_rsrc_t rD = make_rsrc(L.D, L.dpitch * (L.h + 2 * L.dpad) + 256);
-        const __amdgpu_buffer_rsrc_t rJ = make_rsrc(L.J, L.jpitch * (L.h + 2 * L.jpad) + (L.jpad ? 256 : 0));
+        // (a borrowed level 0 has the caller's pitch: the sizes and row offsets are
+        // 32-bit unsigned, exact up to the 2^32 - 1 bytes tbdk_pyr_build_borrowed accepts)
+        const __amdgpu_buffer_rsrc_t rI = make_rsrc(L.I, rsrc_bytes(L.ipitch, hp, L.ipad ? 256 : 0));
+        const __amdgpu_buffer_rsrc_t rD = make_rsrc(L.D, rsrc_bytes(L.dpitch, L.h + 2 * L.dpad, 256));
+        const __amdgpu_buffer_rsrc_t rJ = make_rsrc(L.J, rsrc_bytes(L.jpitch, L.h + 2 * L.jpad, L.jpad ? 256 : 0));
         // the J window rows jy0 .. jy0 + WH at columns jx0 + x, jx0 + x + 1 into jp;
         // on an unpadded level a wave with a window across the edge takes the
         // reflect-101 path (wave-uniform)
@@ -182,9 +184,9 @@
                     jp[r] = on ? load_pair_refl(rJ, L.jpitch, L.w, L.h, jy0 + r, jx0 + x) : 0u;
                 return;
             }
-            const uint32_t joff = on ? (uint32_t)((jy0 + L.jpad) * L.jpitch + jx0 + x + L.jpad) : 0u;
+            const uint32_t joff = on ? (uint32_t)(jy0 + L.jpad) * (uint32_t)L.jpitch + (uint32_t)(jx0 + x + L.jpad) : 0u;
 #pragma unroll
-            for (int r = 0; r <= WH; ++r) jp[r] = load_pair_u8_ua(rJ, joff, r * L.jpitch);
+            for (int r = 0; r <= WH; ++r) jp[r] = load_pair_u8_ua(rJ, joff, (int)((uint32_t)r * (uint32_t)L.jpitch));
         };
 
         nextx -= halfx;
@@ -254,7 +256,8 @@
                 // t0(x+1) - t0(x-1), 3 (t1(x-1) + t1(x+1)) + 10 t1(x) (|Ix|, |Iy|
                 // <= 4080: exact modulo 2^16).  The level's reflect-101 frame is the
                 // reference's row / column reflection.
-                const uint32_t ioff = act ? (uint32_t)((ipy - 1 + L.ipad) * L.ipitch + ipx + x - 1 + L.ipad) : 0u;
+                const uint32_t ioff =
+                    act ? (uint32_t)(ipy - 1 + L.ipad) * (uint32_t)L.ipitch + (uint32_t)(ipx + x - 1 + L.ipad) : 0u;
                 uint32_t u[WH + 3];
                 if (L.ipad == 0 &&
                     any_lane(act && (ipx + x - 1 < 0 || ipx + x + 2 >= L.w || ipy - 1 < 0 || ipy + WH + 1 >= L.h))) {
@@ -264,7 +267,7 @@
                 } else {
 #pragma unroll
                     for (int r = 0; r < WH + 3; ++r)
-                        u[r] = __builtin_amdgcn_raw_buffer_load_b32(rI, ioff, r * L.ipitch, 0);
+                        u[r] = __builtin_amdgcn_raw_buffer_load_b32(rI, ioff, (int)((uint32_t)r * (uint32_t)L.ipitch), 0);
                 }
 #ifdef TBDK_LK_TRACE
                 asm volatile("s_waitcnt vmcnt(0)" ::: "memory");  // the level's source rows have arrived
@@ -675,10 +678,11 @@
                     // an unpadded level: reflect-101 when a window crosses its edge
                     const bool irefl = L.ipad == 0 && any_lane(want && (ipx + x < 0 || ipx + x + 1 >= L.w ||
                                                                         ipy < 0 || ipy + WH >= L.h));
-                    const uint32_t ioff = want ? (uint32_t)((ipy + L.ipad) * L.ipitch + ipx + x + L.ipad) : 0u;
+                    const uint32_t ioff =
+                        want ? (uint32_t)(ipy + L.ipad) * (uint32_t)L.ipitch + (uint32_t)(ipx + x + L.ipad) : 0u;
                     auto irow = [&](int r) -> uint32_t {
                         if (irefl) return want ? load_pair_refl(rI, L.ipitch, L.w, L.h, ipy + r, ipx + x) : 0u;
-                        return load_pair_u8_ua(rI, ioff, r * L.ipitch);
+                        return load_pair_u8_ua(rI, ioff, (int)((uint32_t)r * (uint32_t)L.ipitch));
                     };
                     // row by row (two rows live), packed by row pairs
                     uint32_t ra = irow(0);

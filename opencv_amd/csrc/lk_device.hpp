@@ -61,9 +61,19 @@ __device__ __forceinline__ void bilinear_weights(float fa, float fb, uint32_t& w
     w1 = __builtin_amdgcn_perm(b11, b10, 0x05040100u);
 }
 
-__device__ __forceinline__ __amdgpu_buffer_rsrc_t make_rsrc(const void* base, int bytes)
+// `bytes` is the descriptor's 32-bit unsigned record count.  The library's own
+// levels are far smaller; a level 0 borrowed from the caller is accepted up to
+// pitch * height = 2^32 - 1 bytes (tbdk.h "image layout"), and the row offsets
+// below are exact modulo 2^32 up to that size
+__device__ __forceinline__ __amdgpu_buffer_rsrc_t make_rsrc(const void* base, uint32_t bytes)
 {
-    return __builtin_amdgcn_make_buffer_rsrc(const_cast<void*>(base), (short)0, bytes, 0x00020000);
+    return __builtin_amdgcn_make_buffer_rsrc(const_cast<void*>(base), (short)0, (int)bytes, 0x00020000);
+}
+
+// rows x pitch (+ over-read room) bytes as that record count
+__device__ __forceinline__ uint32_t rsrc_bytes(int pitch, int rows, int room = 0)
+{
+    return (uint32_t)pitch * (uint32_t)rows + (uint32_t)room;
 }
 
 // (pixel off, pixel off+1) of the 8 bytes at aligned offset, as an int16 pair
@@ -97,20 +107,20 @@ __device__ __forceinline__ int refl101(int c, int n)
 // pixels col .. col + 3 of `row` as one dword (byte k = pixel col + k)
 __device__ __forceinline__ uint32_t load4_refl(__amdgpu_buffer_rsrc_t rs, int pitch, int w, int h, int row, int col)
 {
-    const int yo = refl101(row, h) * pitch;
+    const uint32_t yo = (uint32_t)refl101(row, h) * (uint32_t)pitch;
     uint32_t v = 0;
 #pragma unroll
     for (int k = 0; k < 4; ++k)
-        v |= (uint32_t)__builtin_amdgcn_raw_buffer_load_b8(rs, (uint32_t)(yo + refl101(col + k, w)), 0, 0) << (8 * k);
+        v |= (uint32_t)__builtin_amdgcn_raw_buffer_load_b8(rs, yo + (uint32_t)refl101(col + k, w), 0, 0) << (8 * k);
     return v;
 }
 
 // (pixel col, pixel col + 1) of `row` as an int16 pair, as load_pair_u8_ua
 __device__ __forceinline__ uint32_t load_pair_refl(__amdgpu_buffer_rsrc_t rs, int pitch, int w, int h, int row, int col)
 {
-    const int yo = refl101(row, h) * pitch;
-    const uint32_t a = __builtin_amdgcn_raw_buffer_load_b8(rs, (uint32_t)(yo + refl101(col, w)), 0, 0);
-    const uint32_t b = __builtin_amdgcn_raw_buffer_load_b8(rs, (uint32_t)(yo + refl101(col + 1, w)), 0, 0);
+    const uint32_t yo = (uint32_t)refl101(row, h) * (uint32_t)pitch;
+    const uint32_t a = __builtin_amdgcn_raw_buffer_load_b8(rs, yo + (uint32_t)refl101(col, w), 0, 0);
+    const uint32_t b = __builtin_amdgcn_raw_buffer_load_b8(rs, yo + (uint32_t)refl101(col + 1, w), 0, 0);
     return a | (b << 16);
 }
 

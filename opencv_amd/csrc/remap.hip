@@ -316,7 +316,7 @@ int prepare(const tbdk_ctx* ctx, const Image& im, int* inter, int border, const 
     if (im.dw == 0 || im.dh == 0) return 1;
     if (!im.src || !im.dst) return TBDK_EINVAL;
     const int esz = im.pix == TBDK_PIX_U8 ? 1 : 4, px = esz * im.cn;
-    if (im.spitch < im.sw * px || im.dpitch < im.dw * px) return TBDK_EINVAL;
+    if (im.spitch < (int64_t)im.sw * px || im.dpitch < (int64_t)im.dw * px) return TBDK_EINVAL;
     if (esz == 4 && ((reinterpret_cast<uintptr_t>(im.src) | reinterpret_cast<uintptr_t>(im.dst) | (unsigned)im.spitch |
                       (unsigned)im.dpitch) & 3))
         return TBDK_EINVAL;
@@ -409,7 +409,7 @@ int tbdk_remap_flow(tbdk_ctx* ctx, const void* src, int pix, int cn, int src_wid
     if (sign != 1 && sign != -1) return TBDK_EINVAL;
     const int st = prepare(ctx, im, &inter, border, border_value, &a);
     if (st != TBDK_OK) return st < 0 ? st : TBDK_OK;
-    if (!flow || flow_pitch < dst_width * 8 || ((reinterpret_cast<uintptr_t>(flow) | (unsigned)flow_pitch) & 3))
+    if (!flow || flow_pitch < (int64_t)dst_width * 8 || ((reinterpret_cast<uintptr_t>(flow) | (unsigned)flow_pitch) & 3))
         return TBDK_EINVAL;
     if (overlaps(flow, extent(dst_height, flow_pitch, dst_width * 8), dst,
                  extent(dst_height, dst_pitch, dst_width * cn * (pix == TBDK_PIX_U8 ? 1 : 4))))

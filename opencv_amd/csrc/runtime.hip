@@ -548,7 +548,7 @@ int tbdk_pyr_destroy(tbdk_ctx* ctx, tbdk_pyr* pyr)
 int tbdk_pyr_build(tbdk_ctx* ctx, const uint8_t* img, int pitch, tbdk_pyr* pyr, void* stream)
 {
     const int cn = pyr && pyr->cn > 1 ? pyr->cn : 1;
-    if (!ctx || !img || !pyr || pyr->nlevels <= 0 || pitch < pyr->lv[0].width * cn) return TBDK_EINVAL;
+    if (!ctx || !img || !pyr || pyr->nlevels <= 0 || pitch < (int64_t)pyr->lv[0].width * cn) return TBDK_EINVAL;
     if (cn > 1 && pyr->depth == TBDK_DEPTH_16F) return TBDK_EINVAL;
     if (pyr->flags & kPyrL0Borrowed) {  // a borrowed level 0 (tbdk_pyr_build_borrowed): the own buffer again
         tbdk_level& L = pyr->lv[0];
@@ -597,7 +597,8 @@ int tbdk_pyr_build_borrowed(tbdk_ctx* ctx, const uint8_t* img, int pitch, tbdk_p
 int tbdk::pyr_build_borrowed(tbdk_ctx* ctx, const uint8_t* img, int pitch, tbdk_pyr* pyr, hipStream_t s)
 {
     if (!ctx || !img || !pyr || pyr->nlevels <= 0 || pyr->cn > 1 || pyr->depth != TBDK_DEPTH_8U ||
-        !(pyr->flags & TBDK_PYR_NO_DERIVS) || pitch < pyr->lv[0].width || !ctx->opt_pyr_fuse)
+        !(pyr->flags & TBDK_PYR_NO_DERIVS) || pitch < pyr->lv[0].width || !ctx->opt_pyr_fuse ||
+        (int64_t)pitch * pyr->lv[0].height > kDescriptorMaxSpan)  // PyrLK reads level 0 through one descriptor
         return TBDK_EINVAL;
     DeviceGuard g(ctx->device);
     pyr->lv[0].data = const_cast<uint8_t*>(img);
@@ -626,7 +627,7 @@ extern "C" {
 
 int tbdk_pyr_build_f16(tbdk_ctx* ctx, const uint16_t* img, int pitch, tbdk_pyr* pyr, void* stream)
 {
-    if (!ctx || !img || !pyr || pyr->nlevels <= 0 || pyr->depth != TBDK_DEPTH_16F || pitch < 2 * pyr->lv[0].width ||
+    if (!ctx || !img || !pyr || pyr->nlevels <= 0 || pyr->depth != TBDK_DEPTH_16F || pitch < (int64_t)2 * pyr->lv[0].width ||
         pitch % 2 != 0)
         return TBDK_EINVAL;
     DeviceGuard g(ctx->device);
@@ -644,7 +645,7 @@ static int pyr_build_f32_from(tbdk_ctx* ctx, const void* img, int pitch, int byt
 {
     const int cn = pyr && pyr->cn > 1 ? pyr->cn : 1;
     if (!ctx || !img || !pyr || pyr->nlevels <= 0 || pyr->depth != TBDK_DEPTH_32F ||
-        pitch < bytes_per_px * cn * pyr->lv[0].width || pitch % bytes_per_px != 0)
+        pitch < (int64_t)bytes_per_px * cn * pyr->lv[0].width || pitch % bytes_per_px != 0)
         return TBDK_EINVAL;
     DeviceGuard g(ctx->device);
     hipStream_t s = static_cast<hipStream_t>(stream);
@@ -1176,6 +1177,11 @@ int tbdk_gftt_rois_px(tbdk_ctx* ctx, const void* img_, int pix, int width, int h
     std::vector<GfttRoi> tab((size_t)nroi);
     int rc = gftt_prepare(rois, nroi, width, height, p, tab.data(), &plan);
     if (rc != TBDK_OK) return rc;
+    // the eigenvalue walk reads each ROI's rows, and its mask rows, through one buffer descriptor
+    for (const GfttRoi& R : tab)
+        if (rows_span(R.h, pitch, R.w * pix_bytes(pix)) > kDescriptorMaxSpan ||
+            (mask && rows_span(R.h, mask_pitch, R.w) > kDescriptorMaxSpan))
+            return TBDK_EINVAL;
     rc = gftt_reserve(ctx->gftt, ctx->device, nroi, plan.total);  // the wide path's buffers: gftt_launch, when it routes there
     if (rc != TBDK_OK) return rc;
     DeviceGuard g(ctx->device);
@@ -1191,8 +1197,10 @@ static int corner_min_eig_px(tbdk_ctx* ctx, const uint8_t* img, int pix, int wid
                              int dst_pitch, void* stream)
 {
     if (!ctx || !img || !dst || width <= 0 || height <= 0 || !pix_layout_ok(img, pix, width, pitch) ||
-        dst_pitch < width * 4 || dst_pitch % 4 != 0)
+        dst_pitch < (int64_t)width * 4 || dst_pitch % 4 != 0)
         return TBDK_EINVAL;
+    // GFTT's eigenvalue walk over the whole image as one ROI: its rows through one buffer descriptor
+    if (rows_span(height, pitch, width * pix_bytes(pix)) > kDescriptorMaxSpan) return TBDK_EINVAL;
     tbdk_roi roi{0, 0, width, height};
     tbdk_gftt_params p{1, 0.01, 0.0, 3};
     GfttPlan plan;
@@ -1242,7 +1250,7 @@ int tbdk_corner_response_px(tbdk_ctx* ctx, const void* img_, int pix, int width,
 {
     const uint8_t* img = static_cast<const uint8_t*>(img_);
     if (!ctx || !img || !dst || width <= 0 || height <= 0 || !pix_layout_ok(img, pix, width, pitch) ||
-        dst_pitch < width * 4 || dst_pitch % 4 != 0 || block_size < 1 || block_size > 63 || !std::isfinite(harris_k))
+        dst_pitch < (int64_t)width * 4 || dst_pitch % 4 != 0 || block_size < 1 || block_size > 63 || !std::isfinite(harris_k))
         return TBDK_EINVAL;
     if (block_size == 3 && !harris)
         return corner_min_eig_px(ctx, img, pix, width, height, pitch, dst, dst_pitch, stream);

@@ -109,7 +109,7 @@ int tbdk_tbd_step_image(tbdk_tbd_detector* d, const uint8_t* frame, int pitch, i
     if (ndets) *ndets = 0;
     if (!d || !frame || cap < 0 || (cap > 0 && !dets_out)) return TBDK_EINVAL;
     const tbdk_tbd_detect_config& c = d->cfg;
-    if (pitch < c.src_width * c.src_cn) return TBDK_EINVAL;
+    if (pitch < (int64_t)c.src_width * c.src_cn) return TBDK_EINVAL;
     DeviceGuard g(d->ctx->device);
     hipStream_t s = static_cast<hipStream_t>(stream);
     const int W = c.width, H = c.height;

@@ -1538,6 +1538,8 @@ int tbdk_probe_step_profile(double* out, int cap)
 int tbdk_tbd_set_corner_mask(tbdk_tbd* t, const uint8_t* mask, int mask_pitch)
 {
     if (!t || t->stepped || (mask && mask_pitch < t->cfg.width)) return TBDK_EINVAL;
+    // the loop's GFTT reads a ROI's mask rows through one buffer descriptor
+    if (mask && rows_span(t->cfg.height, mask_pitch, t->cfg.width) > kDescriptorMaxSpan) return TBDK_EINVAL;
     t->cmask = mask;
     t->cmask_pitch = mask ? mask_pitch : 0;
     return TBDK_OK;
@@ -1565,6 +1567,9 @@ int tbdk_tbd_run(tbdk_tbd* t, const uint8_t* const* frames, int pitch, int first
     for (int i = 0; i < nframes; ++i)
         if (!frames[i] || det_offsets[i + 1] < det_offsets[i] || det_offsets[i] < 0) return TBDK_EINVAL;
     if (nframes > 0 && det_offsets[nframes] > det_offsets[0] && !dets) return TBDK_EINVAL;
+    // the caller's frames are read through buffer descriptors here: by the GFTT launched
+    // ahead over the next frame (tbd_gftt_ahead) and by PyrLK on a borrowed level 0
+    if (nframes > 0 && (int64_t)pitch * t->cfg.height > kDescriptorMaxSpan) return TBDK_EINVAL;
     // ctx option tbd_borrow_l0: the frames stay valid for the whole call, so
     // their pyramids take them as level 0 (derivative-plane pyramids excepted).
     // Only the several-points-per-wave PyrLK kernel reads a borrowed level 0

@@ -370,6 +370,13 @@ hipError_t launch_synth(const void* poses_dev, int nobj, uint32_t bgseed, int W,
 
 namespace tbdk {
 // ---- GFTT over ROIs (klt_gftt.hip) ----
+// The kernels that read a caller's image through a buffer descriptor (the GFTT
+// eigenvalue walk per ROI, PyrLK on a borrowed level 0) address it with 32-bit
+// unsigned sizes and offsets: the bytes they may span (tbdk.h "image layout")
+constexpr int64_t kDescriptorMaxSpan = 0xFFFFFFFFll;
+// bytes from the first byte of the first row to the end of the last row's pixels
+inline int64_t rows_span(int rows, int pitch, int row_bytes) { return (int64_t)(rows - 1) * pitch + row_bytes; }
+
 struct GfttRoi {
     int x, y, w, h;
     int off;   // first value of this ROI in the eigenvalue plane (rows gftt_epitch(w) floats apart)

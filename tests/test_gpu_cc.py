@@ -134,7 +134,9 @@ def test_pitched_image_and_labels(gpu, noisy, layout):
 
 
 def test_a_1080p_frame_of_the_benchmark_sequence(gpu):
-    """the multi-tile scan (2025 tiles), 64 x 4 pixel workgroups in the thousands and a component of 1.5 M pixels"""
+    """64 x 4 pixel workgroups in the thousands and a component of 1.5 M pixels.  Connectivity 8 with CCL_DEFAULT is
+    the Grana numbering, whose keys are 2 x 2 blocks: 960 x 540 keys in 507 scan tiles of 1024, so the tile scan's
+    loop takes one turn here; test_the_wu_numbering_above_1024_scan_tiles takes the second"""
     from opencv_amd import klt
 
     frames, _ = klt.synth_render(20261015, 1920, 1080, 128, 0, 1, ctx=gpu)
@@ -144,6 +146,24 @@ def test_a_1080p_frame_of_the_benchmark_sequence(gpu):
     rn, rlabels, rstats, rcent = CO.connected_components_with_stats(host, 8, LC.CCL_DEFAULT)
     assert rn > 100 and rstats[1:, 4].max() > 1 << 20
     n, labels, stats, cent = run(gpu, mask, 8, LC.CCL_DEFAULT, rn)
+    assert n == rn and np.array_equal(labels.cpu().numpy(), rlabels)
+    assert np.array_equal(stats, rstats) and CO.same_centroids(cent, rcent)
+
+
+@pytest.mark.parametrize("conn,content", [(4, "noise0.5"), (8, "noise0.3")])
+def test_the_wu_numbering_above_1024_scan_tiles(gpu, conn, content):
+    """The Wu numbering keys every pixel, and the scan of the tile sums (cc_scan_tiles_kernel) takes 1024 tiles of
+    1024 keys a turn, carrying the running total into the next: 1100 x 960 = 1,056,000 pixels are 1032 tiles, the
+    smallest frame of this shape whose last tiles are numbered in the second turn.  Noise keeps the components small
+    (the numpy restatement labels it in a few seconds; at connectivity 8 only below the percolation density) and
+    their number, tens of thousands, far above one turn's: labels, N, stats and centroids bit for bit"""
+    w, h = 1100, 960
+    ntiles = (w * h + 1023) // 1024  # ccl.hip: nkeys = width * height unless Grana, kScanTile = 1024
+    assert w * h > 1 << 20 and ntiles > 1024
+    img = LC.image(content, w, h)
+    rn, rlabels, rstats, rcent = CO.connected_components_with_stats(img, conn, LC.CCL_WU)
+    assert rn > 30000 and rlabels[h - 1].max() > rlabels[:h - 8].max()  # labels first met in the last tiles
+    n, labels, stats, cent = run(gpu, img, conn, LC.CCL_WU, rn)
     assert n == rn and np.array_equal(labels.cpu().numpy(), rlabels)
     assert np.array_equal(stats, rstats) and CO.same_centroids(cent, rcent)
 
