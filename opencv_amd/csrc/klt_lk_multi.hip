@@ -25,6 +25,7 @@
 #include <type_traits>
 
 #include "lk_device.hpp"
+#include "lk_stop.hpp"
 
 namespace tbdk {
 

@@ -14,10 +14,8 @@
     // lane past the last point) is idle with k == P and contributes 0
     const int k = lane == 0 ? P : (lane - 1) / WW;
     const int x = k < P ? lane - 1 - k * WW : 0;
-    // the wave's index in the launch: one wave per workgroup, so the second term
-    // is 0 (written out: it keeps the kernels' instructions exactly as compared
-    // by disassembly, DESIGN.md)
-    const int wave = xcd_swizzle(blockIdx.x, gridDim.x) + (threadIdx.x >> 6);
+    // the wave's index in the launch (one wave per workgroup)
+    const int wave = xcd_swizzle(blockIdx.x, gridDim.x);
     // the point's index in a segmented list (seg_point) and its coordinates: the
     // segment's count and the point are loaded together, the point speculatively
     // (index s * stride + j lies inside segment s's stride-sized row of the
@@ -109,6 +107,10 @@
     const int e4 = 4 * (k * WW + WW), s4 = 4 * (k * WW);  // last lane of the point, lane before its first
     const int rnd9 = __builtin_amdgcn_readfirstlane(1 << (W_BITS1 - 5 - 1));
     const int rnd14 = __builtin_amdgcn_readfirstlane(1 << (W_BITS1 - 1));
+    // the epsilon test's single-precision bounds (lk_stop.hpp), in SGPRs
+    const lkstop::EpsBounds eb0 = lkstop::eps_bounds(a.eps2);
+    const lkstop::EpsBounds eb = {__int_as_float(__builtin_amdgcn_readfirstlane(__float_as_int(eb0.lo))),
+                                  __int_as_float(__builtin_amdgcn_readfirstlane(__float_as_int(eb0.hi)))};
 
     const float FLT_SCALE = 1.f / (1 << 20);
     const float halfx = (WW - 1) * 0.5f, halfy = (WH - 1) * 0.5f;
@@ -163,6 +165,13 @@
         if (!any_lane(act)) continue;
         uint32_t w0, w1;
         bilinear_weights(prevx - ipx, prevy - ipy, w0, w1);
+        // idle lanes (lane 0, lanes past the last point) get zero setup weights:
+        // their interpolated Ix / Iy pairs (gxk, gyk) are then 0 (the rounding
+        // term alone shifts to 0), and so are their partials of the G sums and of
+        // every step's b sums, with no per-step select
+        if constexpr (!DENSE) {
+            if (k >= P) w0 = w1 = 0u;
+        }
 
         uint32_t jp[WH + 1];
         const int hp = L.h + 2 * L.ipad;
@@ -277,9 +286,12 @@
                 // (lkpyramid.cpp:1357).  A zero derivative contributes nothing to the
                 // bilinear sums, so the rule is applied to the derivative weights:
                 // the column halves (x, x+1) outside [0, w) by cm, derivative rows
-                // outside [0, h) by the per-lane row bits vm (three ops a row, for
-                // all waves: a wave-uniform masked / unmasked split needs more
-                // VGPRs than it saves)
+                // outside [0, h) by the per-lane row bits vm (three ops a row).
+                // Only a wave with a stepping point whose derivative rows
+                // ipy .. ipy + WH or columns ipx + x, ipx + x + 1 leave the level
+                // runs the masked row loop (wave-uniform); every other wave's masks
+                // would be all ones, and it takes the plain weights.
+                const bool edge = any_lane(act && (ipx + x < 0 || ipx + x + 1 >= L.w || ipy < 0 || ipy + WH >= L.h));
                 const uint32_t cm = ((unsigned)(ipx + x) < (unsigned)L.w ? 0x0000FFFFu : 0u) |
                                     ((unsigned)(ipx + x + 1) < (unsigned)L.w ? 0xFFFF0000u : 0u);
                 const int rlo = min(max(-ipy, 0), 32), rhi = min(max(L.h - ipy, 0), 32);
@@ -300,40 +312,57 @@
                     dy = as_u32(as_u16x2(smc) - as_u16x2(sma));
                 };
                 // rolling window over the source rows: (m, h, s) of rows j-2, j-1, j
+                auto rows = [&](auto masked) {
+                constexpr bool MASKED = decltype(masked)::value;
+                // each arm takes every source row through a statement of its own:
+                // the two arms' common row terms are then not hoisted above the
+                // branch, where all of them would be live at once
+                auto srca = [&](int j, uint32_t& mid, uint32_t& hd, uint32_t& sm) {
+                    if constexpr (MASKED) asm volatile("; masked row" : "+v"(u[j]));
+                    else asm volatile("; plain row" : "+v"(u[j]));
+                    src(j, mid, hd, sm);
+                };
                 uint32_t m0, h0, s0, m1, h1, s1, m2, h2, s2;
-                src(0, m0, h0, s0);
-                src(1, m1, h1, s1);
-                src(2, m2, h2, s2);
+                srca(0, m0, h0, s0);
+                srca(1, m1, h1, s1);
+                srca(2, m2, h2, s2);
                 uint32_t dxa, dya;
                 drow(h0, h1, h2, s0, s2, dxa, dya);  // derivative row 0
                 uint32_t ipa = m1;                   // I row 0
-                uint32_t ra = rowbit(0);
+                uint32_t ra = MASKED ? rowbit(0) : 0u;
 #pragma unroll
                 for (int q = 0; q < NP; ++q) {
                     const int r = 2 * q;
                     // rows r+1 (source r+3) and r+2 (source r+4)
                     m0 = m1; h0 = h1; s0 = s1;
                     m1 = m2; h1 = h2; s1 = s2;
-                    src(r + 3, m2, h2, s2);
+                    srca(r + 3, m2, h2, s2);
                     uint32_t dxb, dyb, dxc = 0, dyc = 0, ipc = 0;
                     drow(h0, h1, h2, s0, s2, dxb, dyb);
                     const uint32_t ipb = m1;
-                    const uint32_t rb = rowbit(r + 1);
+                    const uint32_t rb = MASKED ? rowbit(r + 1) : 0u;
                     uint32_t rc = 0;
                     if (r + 1 < WH) {
                         m0 = m1; h0 = h1; s0 = s1;
                         m1 = m2; h1 = h2; s1 = s2;
-                        src(r + 4, m2, h2, s2);
+                        srca(r + 4, m2, h2, s2);
                         drow(h0, h1, h2, s0, s2, dxc, dyc);
                         ipc = m1;
-                        rc = rowbit(r + 2);
+                        if constexpr (MASKED) rc = rowbit(r + 2);
                     }
-                    pair_step(q, ipa, ipb, ipc, dxa, dxb, dxc, dya, dyb, dyc, wd0 & ra, wd1 & rb, wd0 & rb, wd1 & rc);
+                    if constexpr (MASKED)
+                        pair_step(q, ipa, ipb, ipc, dxa, dxb, dxc, dya, dyb, dyc, wd0 & ra, wd1 & rb, wd0 & rb, wd1 & rc);
+                    else
+                        pair_step(q, ipa, ipb, ipc, dxa, dxb, dxc, dya, dyb, dyc, w0, w1, w0, w1);
                     ipa = ipc;
                     dxa = dxc;
                     dya = dyc;
                     ra = rc;
                 }
+                };
+                if (edge) rows(std::true_type{});
+                else rows(std::false_type{});
+                __builtin_amdgcn_sched_barrier(0);  // (the masked arm's temporaries end here)
             } else if constexpr (DENSE) {
                 // the window from case image (gx, gy) mod 2^level: element (r, x) at
                 // level position (ipy + r, ipx + x); per row pair two 8-byte loads
@@ -388,7 +417,9 @@
             if (level == a.max_level) tr_stamp(15);  // the first level's window terms done (before the G sums)
             __builtin_amdgcn_sched_barrier(0);
 #endif
-            if (k >= P) acc[0] = acc[1] = acc[2] = 0;
+            if constexpr (DENSE) {  // (the case images' pairs are not made from the weights)
+                if (k >= P) acc[0] = acc[1] = acc[2] = 0;
+            }
             float s[3];
 #ifdef TBDK_LK_TRACE
             bool tr_split = false;
@@ -424,7 +455,10 @@
         }
         D = 1.f / D;
 
-        float pdx = 0.f, pdy = 0.f;
+        // the previous step's delta; before the first step +Inf, so that the
+        // oscillation test |dd + pd| <= 0.01f is false there as the reference's
+        // `j > 0 &&` makes it (dd + Inf is +Inf, or NaN for dd = -Inf / NaN)
+        float pdx = __builtin_inff(), pdy = __builtin_inff();
         // The remaining Newton steps of point ks, the wave's only active one, from
         // step j on (the stepping of the loop below, the same integers and float
         // operations): its window's rows are dealt to the P lane groups, group g
@@ -521,8 +555,8 @@
                         d = pack_diff(bilin_c(jp2[2 * t], jp2[2 * t + 1], v0, v1, ic2[2 * t]),
                                       bilin_c(jp2[2 * t + 1], jp2[2 * t + 2], v0, v1, ic2[2 * t + 1]));
                     }
-                    b[0] = sdot2(d, gx2[t], b[0]);
-                    b[1] = sdot2(d, gy2[t], b[1]);
+                    b[0] = t ? sdot2(d, gx2[t], b[0]) : sdot2_first(d, gx2[t]);
+                    b[1] = t ? sdot2(d, gy2[t], b[1]) : sdot2_first(d, gy2[t]);
                 }
                 float fb[2];
                 seg_sum_exact<2, 25>(b, 4 * (P * WW), 0, fb);  // lanes 1 .. P*WW (lane 0 adds 0)
@@ -534,8 +568,20 @@
                 sny += ddy;
                 sox = snx + halfx;
                 soy = sny + halfy;
-                if ((double)ddx * ddx + (double)ddy * ddy <= a.eps2) break;
-                if (j > 0 && (double)fabsf(ddx + spdx) < 0.01 && (double)fabsf(ddy + spdy) < 0.01) {
+                // the stopping tests in single precision (lk_stop.hpp; the values
+                // are the point's, uniform over the wave)
+                const float q = lkstop::eps_q(ddx, ddy);
+                const uint64_t belowm = __builtin_amdgcn_ballot_w64(lkstop::eps_below(q, eb));
+                const uint64_t abovem = __builtin_amdgcn_ballot_w64(lkstop::eps_above(q, eb));
+                bool reached = belowm != 0;
+                if ((belowm | abovem) == 0) {  // ambiguous
+                    asm volatile("" ::: "memory");  // a real branch: the double ops are not speculated
+                    reached = __builtin_amdgcn_ballot_w64(lkstop::eps_exact(ddx, ddy, a.eps2)) != 0;
+                }
+                if (reached) break;
+                // (first step: pd = +Inf)
+                if ((__builtin_amdgcn_ballot_w64(lkstop::osc_small(ddx + spdx)) &
+                     __builtin_amdgcn_ballot_w64(lkstop::osc_small(ddy + spdy))) != 0) {
                     sox -= ddx * 0.5f;
                     soy -= ddy * 0.5f;
                     break;
@@ -555,46 +601,49 @@
             }
             act = false;
         };
-        for (int j = 0; j < a.max_count; ++j) {
-            if (!any_lane(act)) break;
+        // The loop has one exit, at its bottom (steps left, a point still
+        // stepping, no hand-over to the one-point steps), and every per-point
+        // update in it is a select: with the hand-over's break at the top and
+        // masked update blocks the compiler kept two copies of the loop-carried
+        // values and moved them (9 v_mov a step).
+        // The set of points still stepping is a lane mask in SGPRs (actm), and
+        // every test of the step is the ballot of one compare, combined by scalar
+        // ops: the ballot of a combined per-lane bool is first made a 0 / 1 VGPR
+        // and compared again (two VALU each, for the loop's condition, the reload
+        // test, the band test and the hand-over).
+        const auto bal = [](bool p) { return __builtin_amdgcn_ballot_w64(p); };
+        uint64_t actm = bal(act);
+        const uint64_t headm = bal(x == 0 && k < P);  // the points' first lanes
+        int solo_ks = -1, solo_j = 0;
+        for (int j = 0; j < a.max_count && actm != 0;) {
 #ifdef TBDK_LK_TRACE
             ++tr_steps;
 #endif
-            if constexpr (kSoloOk) {
-                // one point left stepping (LkArgs::solo_min): its remaining steps
-                // on all the wave's lanes, the window rows split over the P lane
-                // groups (solo_steps); then the level's Newton phase is over
-                if (a.solo_min > 0 && j >= a.solo_min && L.jpad > 0) {
-                    const uint64_t heads = __builtin_amdgcn_ballot_w64(act && x == 0 && k < P);
-                    if (__builtin_popcountll(heads) == 1) {
-                        solo_steps((__builtin_ctzll(heads) - 1) / WW, j);
-                        break;
-                    }
-                }
-            }
             const int inx = (int)floorf(nextx), iny = (int)floorf(nexty);
-            if (act && (inx < -WW || inx >= L.w || iny < -WH || iny >= L.h)) {
-                if (level == 0) status = 0;
-                act = false;
+            {
+                const uint64_t oobm = bal(inx < -WW) | bal(inx >= L.w) | bal(iny < -WH) | bal(iny >= L.h);
+                status = __builtin_amdgcn_inverse_ballot_w64(level == 0 ? actm & oobm : 0ull) ? 0 : status;
+                actm &= ~oobm;
             }
+            const bool on = __builtin_amdgcn_inverse_ballot_w64(actm);  // this lane's point steps
 #ifdef TBDK_LK_PROBE_ITERS_LV  // probe builds: the Newton steps per level, 8 bits each (level L at bit 8L)
-            nit += act ? 1 << (8 * level) : 0;
+            nit += on ? 1 << (8 * level) : 0;
 #else
-            nit += act ? 1 : 0;
+            nit += on ? 1 : 0;
 #endif
-            const bool moved = act && (inx != pinx || iny != piny);
+            const uint64_t movedm = (bal(inx != pinx) | bal(iny != piny)) & actm;
 #ifdef TBDK_LK_PROBE_RELOADS  // tuning builds: 1 always reloads, 2 counts reloads into iters, 3 never reloads
 #if TBDK_LK_PROBE_RELOADS == 2
-            nrl += any_lane(moved) ? 1 : 0;
+            nrl += movedm != 0 ? 1 : 0;
 #endif
-            if (TBDK_LK_PROBE_RELOADS == 1 || (TBDK_LK_PROBE_RELOADS != 3 && any_lane(moved))) {
+            if (TBDK_LK_PROBE_RELOADS == 1 || (TBDK_LK_PROBE_RELOADS != 3 && movedm != 0)) {
 #else
-            if (any_lane(moved)) {  // uniform: reload the J columns (unchanged for points that did not move)
+            if (movedm != 0) {  // uniform: reload the J columns (unchanged for points that did not move)
 #endif
 #ifdef TBDK_LK_TRACE
                 ++tr_reloads;
 #endif
-                load_j(act, inx, iny);
+                load_j(on, inx, iny);
                 pinx = inx;
                 piny = iny;
             }
@@ -621,9 +670,8 @@
                                                bilin_c(jp[r + 1], jp[r + 2], w0, w1, ic[r + 1]))
                                    : pack_diff(bilin_c(jp[r], jp[r + 1], w0, w1, ic[r]), 0);
                 }
-                const uint32_t gx = gxk[q], gy = gyk[q];
-                b[0] = sdot2(d, gx, b[0]);
-                b[1] = sdot2(d, gy, b[1]);
+                b[0] = q ? sdot2(d, gxk[q], b[0]) : sdot2_first(d, gxk[q]);
+                b[1] = q ? sdot2(d, gyk[q], b[1]) : sdot2_first(d, gyk[q]);
 #ifdef TBDK_LK_NEWTON_SB
                 if (q % TBDK_LK_NEWTON_SB == TBDK_LK_NEWTON_SB - 1) __builtin_amdgcn_sched_barrier(0);
 #endif
@@ -634,27 +682,66 @@
                 b[0] -= cgx;
                 b[1] -= cgy;
             }
-            if (k >= P) b[0] = b[1] = 0;
+            if constexpr (DENSE) {  // (elsewhere the idle lanes' gxk / gyk are 0: the setup weights)
+                if (k >= P) b[0] = b[1] = 0;
+            }
             float fb[2];
             seg_sum_exact<2>(b, e4, s4, fb);
             const float fb1 = fb[0] * FLT_SCALE;
             const float fb2 = fb[1] * FLT_SCALE;
             const float ddx = (A12 * fb2 - A22 * fb1) * D;
             const float ddy = (A12 * fb1 - A11 * fb2) * D;
-            if (act) {
-                nextx += ddx;
-                nexty += ddy;
-                outx = nextx + halfx;
-                outy = nexty + halfy;
-                if ((double)ddx * ddx + (double)ddy * ddy <= a.eps2) {
-                    act = false;
-                } else if (j > 0 && (double)fabsf(ddx + pdx) < 0.01 && (double)fabsf(ddy + pdy) < 0.01) {
-                    outx -= ddx * 0.5f;
-                    outy -= ddy * 0.5f;
-                    act = false;
+            // The stopping tests in single precision (lk_stop.hpp): the double
+            // expression only in a wave where some stepping point's q lies in the
+            // band around eps2 that q's roundings cannot decide (wave-uniform; the
+            // exact test has the prefilter's value wherever that one decides).
+            const float q = lkstop::eps_q(ddx, ddy);
+            const uint64_t belowm = bal(lkstop::eps_below(q, eb)), abovem = bal(lkstop::eps_above(q, eb));
+            uint64_t reachm = belowm;
+            if ((~(belowm | abovem) & actm) != 0) {  // some stepping point's q is ambiguous
+                asm volatile("" ::: "memory");  // a real branch: the double ops are not speculated
+                reachm = bal(lkstop::eps_exact(ddx, ddy, a.eps2));
+            }
+            // (first step: pd = +Inf)
+            const uint64_t oscm = bal(lkstop::osc_small(ddx + pdx)) & bal(lkstop::osc_small(ddy + pdy));
+            // The update as selects for the stepping points, not a masked block (the
+            // compiler copied the six loop-carried values in front of one).  pdx /
+            // pdy are read only for a point that still steps: no select.
+            const float nx = nextx + ddx, ny = nexty + ddy;
+            float ox = nx + halfx, oy = ny + halfy;
+            if (__builtin_amdgcn_inverse_ballot_w64(oscm & ~reachm)) {
+                ox -= ddx * 0.5f;
+                oy -= ddy * 0.5f;
+            }
+            nextx = on ? nx : nextx;
+            nexty = on ? ny : nexty;
+            outx = on ? ox : outx;
+            outy = on ? oy : outy;
+            actm &= ~(reachm | oscm);
+            pdx = ddx;
+            pdy = ddy;
+            ++j;
+            if constexpr (kSoloOk) {
+                // one point left stepping (LkArgs::solo_min): its remaining steps
+                // on all the wave's lanes, the window rows split over the P lane
+                // groups (solo_steps, below the loop); then the level's Newton
+                // phase is over
+                if (a.solo_min > 0 && j >= a.solo_min && L.jpad > 0) {
+                    const uint64_t heads = actm & headm;
+                    if (__builtin_popcountll(heads) == 1) {
+                        solo_ks = (__builtin_ctzll(heads) - 1) / WW;
+                        solo_j = j;
+                        break;
+                    }
                 }
-                pdx = ddx;
-                pdy = ddy;
+            }
+        }
+        if constexpr (kSoloOk) {
+            if (solo_ks >= 0 && solo_j < a.max_count) {
+#ifdef TBDK_LK_TRACE
+                ++tr_steps;
+#endif
+                solo_steps(solo_ks, solo_j);
             }
         }
 

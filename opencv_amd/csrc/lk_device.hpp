@@ -23,6 +23,15 @@ __device__ __forceinline__ int sdot2(uint32_t a, uint32_t b, int c)
     return __builtin_amdgcn_sdot2(__builtin_bit_cast(s16x2, a), __builtin_bit_cast(s16x2, b), c, false);
 }
 
+// a . b alone: the three-operand form with the constant 0 (started from a zero
+// accumulator, the compiler clears a VGPR with a v_mov for v_dot2c first)
+__device__ __forceinline__ int sdot2_first(uint32_t a, uint32_t b)
+{
+    int t;
+    asm("v_dot2_i32_i16 %0, %1, %2, 0" : "=v"(t) : "v"(a), "v"(b));
+    return t;
+}
+
 // bilinear of a packed pixel pair on two rows: (p0 . w0 + p1 . w1 + round) >> shift
 // (the reference's _mm_madd_epi16 products and CV_DESCALE, lkpyramid.cpp:288-303)
 __device__ __forceinline__ int bilin(uint32_t p0, uint32_t p1, uint32_t w0, uint32_t w1, int shift)
