@@ -25,6 +25,7 @@
 #include <type_traits>
 
 #include "lk_device.hpp"
+#include "lk_int_origin.hpp"
 #include "lk_stop.hpp"
 
 namespace tbdk {
@@ -179,6 +180,12 @@ __device__ __forceinline__ bool any_lane(bool p) { return __builtin_amdgcn_ballo
 #ifndef TBDK_LK_IPACK_FLY
 #define TBDK_LK_IPACK_FLY 0  // Scharr-on-the-fly instance
 #endif
+// The Scharr-on-the-fly setup's arm for waves whose windows all have an integer
+// origin at the level (lk_int_origin.hpp; the same results).  0 compiles it out,
+// for tools/lk_valu_count.py to count the kernel without it.
+#ifndef TBDK_LK_INT_ORIGIN
+#define TBDK_LK_INT_ORIGIN 1
+#endif
 
 // Probe builds (-DTBDK_LK_TRACE, tools/probe_lk_trace.py): every wave writes
 // one record of sixteen u64 (at its launch's base + its wave index, no atomics:
@@ -191,9 +198,10 @@ __device__ __forceinline__ bool any_lane(bool p) { return __builtin_amdgcn_ballo
 // waits for it there), [4L+3] its Newton steps done; [12] the error pass done;
 // [13] the point's coordinates arrived (start: the wave's first instruction),
 // [14] the first level's source rows arrived (FLY; the probe waits for them
-// there), [15] its window terms done (before the G sums); bits 48.. of the
-// steps word: the levels whose G sums took seg_sum_exact's split path.  Not in
-// the product library.
+// there), [15] its window terms done (before the G sums); bits 48..55 of the
+// steps word: the levels whose G sums took seg_sum_exact's split path, bits
+// 56..63: the levels whose setup took the integer-origin arm.  Not in the
+// product library.
 #ifdef TBDK_LK_TRACE
 __device__ unsigned long long* g_lk_trace;
 __device__ unsigned int g_lk_trace_cap;

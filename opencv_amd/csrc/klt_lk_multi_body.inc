@@ -92,6 +92,7 @@
 #ifdef TBDK_LK_TRACE
     int tr_steps = 0, tr_reloads = 0;
     unsigned tr_gsplit = 0;  // levels whose G sums took seg_sum_exact's split path
+    unsigned tr_int = 0;     // levels whose setup took the integer-origin arm
     auto tr_stamp = [&](int idx) {
         const unsigned r = a.trace_base + (unsigned)wave;
         const unsigned d = (unsigned)(__builtin_amdgcn_s_memrealtime() - tr_t0);
@@ -314,12 +315,16 @@
                 // rolling window over the source rows: (m, h, s) of rows j-2, j-1, j
                 auto rows = [&](auto masked) {
                 constexpr bool MASKED = decltype(masked)::value;
-                // each arm takes every source row through a statement of its own:
-                // the two arms' common row terms are then not hoisted above the
-                // branch, where all of them would be live at once
+                // the masked arm (and the integer-origin arm below) takes every
+                // source row through a statement of its own: the arms' common row
+                // terms are then not hoisted above the branch, where all of them
+                // would be live at once.  The plain arm reads the rows as they are
+                // (its statement is a marker for tools/lk_valu_count.py): the rows
+                // stay live past it into the arm laid out next, and a statement that
+                // redefined them here would cost a copy each.
                 auto srca = [&](int j, uint32_t& mid, uint32_t& hd, uint32_t& sm) {
                     if constexpr (MASKED) asm volatile("; masked row" : "+v"(u[j]));
-                    else asm volatile("; plain row" : "+v"(u[j]));
+                    else asm volatile("; plain row");
                     src(j, mid, hd, sm);
                 };
                 uint32_t m0, h0, s0, m1, h1, s1, m2, h2, s2;
@@ -360,8 +365,43 @@
                     ra = rc;
                 }
                 };
-                if (edge) rows(std::true_type{});
-                else rows(std::false_type{});
+                // Integer origin (lk_int_origin.hpp): no stepping lane's window
+                // leaves the level and every stepping lane's weights are those of a
+                // zero fraction (wave-uniform; lanes that do not step, the idle
+                // lanes with their zero weights among them, are not asked).  The
+                // window terms are then the Scharr values and the pixels of column
+                // x themselves, made by row pairs with no interpolation; an idle
+                // lane's factors are 0, so its gxk / gyk are 0 here as well.
+                // Forward instances only: a backward pass starts from forward
+                // results.  The rows through a statement of this arm's own, as in
+                // the masked arm.
+                bool inta = false;
+#if TBDK_LK_INT_ORIGIN
+                if constexpr (!BACK) inta = !any_lane(act && (w0 != lkint::kW0 || w1 != lkint::kW1));
+#endif
+                if (edge) {
+                    rows(std::true_type{});
+                } else if (__builtin_expect(inta, 1)) {
+#ifdef TBDK_LK_TRACE
+                    tr_int |= 1u << level;
+#endif
+#pragma unroll
+                    for (int j = 0; j < WH + 2; ++j) asm volatile("; integer-origin row" : "+v"(u[j]));
+                    uint32_t ipl[ILIN ? NP : 1];
+                    lkint::column<WH, IM>(u, lkint::factors(k < P), rnd9, ic, ILIN ? ipl : ipk, gxk, gyk);
+#pragma unroll
+                    for (int q = 0; q < NP; ++q) {
+                        if constexpr (ILIN) {
+                            cgx = sdot2(ipl[q], gxk[q], cgx);
+                            cgy = sdot2(ipl[q], gyk[q], cgy);
+                        }
+                        acc[0] = sdot2(gxk[q], gxk[q], acc[0]);
+                        acc[1] = sdot2(gxk[q], gyk[q], acc[1]);
+                        acc[2] = sdot2(gyk[q], gyk[q], acc[2]);
+                    }
+                } else {
+                    rows(std::false_type{});
+                }
                 __builtin_amdgcn_sched_barrier(0);  // (the masked arm's temporaries end here)
             } else if constexpr (DENSE) {
                 // the window from case image (gx, gy) mod 2^level: element (r, x) at
@@ -837,7 +877,8 @@
                                       : (unsigned long long)(uintptr_t)(a.seg_list ? (const void*)a.seg_list
                                                                                    : (const void*)a.prev_pts);
                 o[5] = (unsigned)tr_steps | ((unsigned long long)(unsigned)tr_reloads << 16) |
-                       ((unsigned long long)(unsigned)mx << 32) | ((unsigned long long)tr_gsplit << 48);
+                       ((unsigned long long)(unsigned)mx << 32) | ((unsigned long long)(tr_gsplit & 0xFFu) << 48) |
+                       ((unsigned long long)(tr_int & 0xFFu) << 56);
             }
         }
     }

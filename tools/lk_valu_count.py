@@ -7,9 +7,15 @@ line (taken from a dry run of make, the object's `-c -o` replaced by device-only
 `-S`) and prints, for the window-W forward Scharr-on-the-fly instance
 (lk_multi_kernel<W, W, true, false>, default W = 21):
 
-  * setup: the VALU instructions of the level setup's window block, found as the
-    basic block with the most v_dot2* (and of the runner-up when that holds at
-    least half as many: the second arm of a setup that is split by a branch);
+  * setup: the VALU instructions of each arm of the level setup's window block
+    (plain, masked, integer origin), found by the marker comments the arms'
+    source rows pass through (klt_lk_multi_body.inc; EXTRA=-DTBDK_LK_INT_ORIGIN=0
+    in the environment builds the kernel without the integer-origin arm); with
+    no marker in the assembly, the basic block with the most v_dot2* (and the
+    runner-up when that holds at least half as many).  Work the compiler moves
+    below the arms' join is in no arm's count: with two arms the 42 VALU that
+    turn the I sums into ic (mask and subtract per row) sat there, with three
+    they are inside the plain and the masked arm;
   * step / solo step: the VALU instructions on the cheapest way (by VALU count)
     from a block that holds v_add_u32_dpp (the b-sum scans) once round and back
     to it, not through the setup: the Newton step of all the wave's points (the
@@ -32,6 +38,7 @@ import tempfile
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 CSRC = os.path.join(ROOT, "opencv_amd", "csrc")
+ARMS = {"; plain row": "plain arm", "; masked row": "masked arm", "; integer-origin row": "integer-origin arm"}
 BRANCH = re.compile(r"^(s_cbranch_\w+|s_branch)\s+(\S+)")
 
 
@@ -76,13 +83,13 @@ def functions(path):
 def blocks(lines):
     """basic blocks: [(labels, instructions)], split at labels, at the
     compiler's block comments and after every branch"""
-    out, labels, ins = [], [], []
+    out, labels, ins, marks = [], [], [], set()
 
     def flush():
-        nonlocal labels, ins
+        nonlocal labels, ins, marks
         if labels or ins:
-            out.append((labels, ins))
-        labels, ins = [], []
+            out.append((labels, ins, marks))
+        labels, ins, marks = [], [], set()
 
     for ln in lines:
         m = re.match(r"^(\.LBB\w+):", ln)
@@ -92,6 +99,8 @@ def blocks(lines):
             if m:
                 labels.append(m.group(1))
             continue
+        if ln in ARMS:
+            marks.add(ARMS[ln])
         if ln.startswith(";") or ln.startswith("."):
             continue
         ins.append(ln.split(";")[0].strip())
@@ -108,9 +117,9 @@ def count(ins, prefix="v_"):
 def analyse(lines):
     bl = blocks(lines)
     n = len(bl)
-    at = {lb: i for i, (lbs, _) in enumerate(bl) for lb in lbs}
+    at = {lb: i for i, (lbs, _, _) in enumerate(bl) for lb in lbs}
     succ = [[] for _ in range(n)]
-    for i, (_, ins) in enumerate(bl):
+    for i, (_, ins, _) in enumerate(bl):
         m = BRANCH.match(ins[-1]) if ins else None
         # a branch on exec only skips a masked region no lane needs: the count
         # follows the region (the fall-through)
@@ -118,13 +127,16 @@ def analyse(lines):
             succ[i].append(at[m.group(2)])
         if not (m and m.group(1) == "s_branch") and not (ins and ins[-1].startswith("s_endpgm")) and i + 1 < n:
             succ[i].append(i + 1)
-    valu = [count(ins) for _, ins in bl]
-    dot2 = [count(ins, "v_dot2") for _, ins in bl]
-    dpp = [sum(1 for i in ins if i.startswith("v_add_u32_dpp")) for _, ins in bl]
+    valu = [count(ins) for _, ins, _ in bl]
+    dot2 = [count(ins, "v_dot2") for _, ins, _ in bl]
+    dpp = [sum(1 for i in ins if i.startswith("v_add_u32_dpp")) for _, ins, _ in bl]
 
     # setup: the block(s) with the most v_dot2*
     order = sorted(range(n), key=lambda i: -dot2[i])
     setup = [order[0]] + [i for i in order[1:2] if 2 * dot2[i] >= dot2[order[0]]]
+    marked = [i for i in range(n) if bl[i][2]]
+    if marked:
+        setup = marked
 
     # one step = the cheapest way (by VALU count) from a block that holds the
     # b-sum scans round the Newton loop and back to it, not through the setup
@@ -152,9 +164,12 @@ def analyse(lines):
                 f64 = sum(1 for i in path for x in bl[i][1] if x.startswith("v_") and "f64" in x.split()[0])
                 steps[d2] = {"valu": c, "dot2": d2, "f64": f64, "dpp": sum(dpp[i] for i in path),
                              "blocks": [(bl[i][0] or ["(fallthrough)"])[0] for i in path]}
-    steps = list(steps.values())
+    # a step's b sums are two scans of six DPP adds each: a way round with more
+    # goes through another level's setup (its G sums), not round the Newton loop
+    steps = [s for s in steps.values() if s["dpp"] == 12]
     steps.sort(key=lambda s: -s["dot2"])
-    return {"setup": [{"block": (bl[i][0] or ["(fallthrough)"])[0], "valu": valu[i], "dot2": dot2[i]} for i in setup],
+    return {"setup": [{"block": (bl[i][0] or ["(fallthrough)"])[0], "valu": valu[i], "dot2": dot2[i],
+                       "arm": ", ".join(sorted(bl[i][2]))} for i in setup],
             "steps": steps}
 
 
@@ -174,7 +189,7 @@ def main():
     r = analyse(fns[name])
     print(f"{name}: {vgprs.get(name)} VGPRs")
     for s in r["setup"]:
-        print(f"  setup block {s['block']}: {s['valu']} VALU ({s['dot2']} v_dot2*)")
+        print(f"  setup{', ' + s['arm'] if s['arm'] else ''} (block {s['block']}): {s['valu']} VALU ({s['dot2']} v_dot2*)")
     for k, s in enumerate(r["steps"]):
         tag = "step (all points)" if k == 0 else "solo step" if k == len(r["steps"]) - 1 else "step (other)"
         print(f"  {tag}: {s['valu']} VALU on the cheapest way round ({s['dot2']} v_dot2*, {s['f64']} f64, "

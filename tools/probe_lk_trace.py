@@ -1,7 +1,8 @@
 """Per-wave timeline of the lk_multi launches (probe build with -DTBDK_LK_TRACE:
 opencv_amd/lib/libtbdk_trace.so, selected by TBDK_LIB).  Each wave records its
 start / end (s_memrealtime, 10 ns), HW_ID / XCC_ID, its Newton steps, J reloads
-and the max iterations of its points.
+the max iterations of its points and the levels whose setup took the
+integer-origin arm (lk_int_origin.hpp).
 
   loop        the TBD loop of bench.py's configs[2] (1080p x 128), frames
               [20, 20 + F) traced, every PyrLK launch of the frame
@@ -68,6 +69,7 @@ def summarize(rec, label=""):
     steps = (rec[:, 5] & 0xFFFF).astype(np.int64)
     rel = ((rec[:, 5] >> 16) & 0xFFFF).astype(np.int64)
     mit = ((rec[:, 5] >> 32) & 0xFFFF).astype(np.int64)
+    arm = int_origin_share(rec)
     ends = np.sort(en)
     q = lambda f: ends[min(len(ends) - 1, int(f * len(ends)))]
     simd = (rec[:, 2] & 0xFFFFFFFF).astype(np.int64)
@@ -103,11 +105,20 @@ def summarize(rec, label=""):
          f"waves/SIMD mean {occ:.2f} (SIMDs used {uniq}); resident peak {o.max():.0f}; "
          f"steps mean {steps.mean():.1f} max {steps.max()}; reloads mean {rel.mean():.2f}; maxit mean {mit.mean():.1f}\n")
     s += "   phases (mean us): " + "; ".join(phs) + "\n"
+    s += "   integer-origin arm, share of waves: " + " ".join(f"L{L} {v:.3f}" for L, v in arm) + "\n"
     s += "   occupancy by 10%% of span: " + " ".join(
         f"{o[int(i * nb / 10):int((i + 1) * nb / 10)].mean() / 1024:.2f}" for i in range(10)) + "\n"
     s += "   last waves (start, dur, steps, reloads, maxit): " + "; ".join(
         f"({st[i]:.1f}, {dur[i]:.1f}, {steps[i]}, {rel[i]}, {mit[i]})" for i in last)
     return s
+
+
+def int_origin_share(rec):
+    """[(level, share of the waves whose setup took the integer-origin arm there)]
+    for the levels the waves ran (bits 56.. of the steps word)"""
+    bits = (rec[:, 5] >> np.uint64(56)).astype(np.int64)
+    ph = rec[:, 6:14].copy().view(np.uint32)
+    return [(L, float((bits >> L & 1).mean())) for L in (2, 1, 0) if (ph[:, 4 * L + 3] > 0).any()]
 
 
 def run_loop(lib, buf, frames_traced):
@@ -189,7 +200,8 @@ def main():
     rec = run_loop(lib, buf, int(sys.argv[2]) if len(sys.argv) > 2 else 20)
     np.savez_compressed("gpurun_out/lk_trace_loop.npz", rec=rec)
     ls = split_launches(rec)
-    print(f"loop: {len(rec)} wave records, {len(ls)} launches", flush=True)
+    print(f"loop: {len(rec)} wave records, {len(ls)} launches; integer-origin arm, share of all waves: " +
+          " ".join(f"L{L} {v:.4f}" for L, v in int_origin_share(rec)), flush=True)
     for key, l in ls:
         print(summarize(l, f"[key {key[0] & 0xFFFFF:x} n {key[1]}]"), flush=True)
 
