@@ -1675,6 +1675,76 @@ int tbdk_mog2_get_model(tbdk_mog2* m, float* weight, float* variance, float* mea
 /* frames applied since the model was last cleared */
 int tbdk_mog2_frames(tbdk_mog2* m, int* nframes);
 
+/* cv::BackgroundSubtractorKNN, the CPU class of video/src/bgfg_KNN.cpp (not its OpenCL twin, whose
+ * samples are floats), with its model resident on the device: per pixel 3 * nsamples samples of
+ * `channels` bytes and an include flag in three circular lists (short, mid, long), an index byte
+ * and a "next update" byte per list.  One kernel per frame classifies every pixel and updates its
+ * model; the next-update planes are redrawn on the device by cv::randu's own generator, with the
+ * reference's sequence and its count of consumed steps (blocks of 1024 values, started by
+ * jump-ahead).  Mask, background image, model, counters and RNG state are the reference's bit for
+ * bit.  Frames: 8-bit, 1 or 3 channels, pitched, any alignment.  The reference reads a frame of
+ * another depth as raw bytes; that is not reproduced, and neither are four channels. */
+typedef struct tbdk_knn tbdk_knn;
+
+typedef struct tbdk_knn_config {
+    int32_t width, height, channels;  /* fixed at creation */
+    int32_t history;                /* 500 */
+    int32_t nsamples;               /* 7 (nN); 1..16, fixed at creation */
+    int32_t knn_samples;            /* 2 (nkNN): MAX(1, cvRound(0.1 * nN * 3 + 0.40)) of the default nN;
+                                       as in the reference, another nsamples does not change it */
+    int32_t detect_shadows;         /* 1 */
+    int32_t shadow_value;           /* 127; 0..255 */
+    float   dist2_threshold;        /* 400 (fTb) */
+    float   shadow_threshold;       /* 0.5 (fTau) */
+    uint64_t rng_state;             /* 0xffffffff, a fresh thread's cv::theRNG(); read at creation only */
+} tbdk_knn_config;
+
+/* the reference's defaults for a frame of this size and channel count */
+int tbdk_knn_config_default(int width, int height, int channels, tbdk_knn_config* cfg);
+/* Allocates the model (nothing is allocated afterwards; nothing is copied or synchronised: the
+ * first fill takes rng_state as an argument).  TBDK_EINVAL:
+ * channels other than 1 / 3, nsamples outside 1..16, width or height outside 1..65535, history < 1,
+ * shadow_value outside 0..255, a NaN threshold. */
+int tbdk_knn_create(tbdk_ctx* ctx, const tbdk_knn_config* cfg, tbdk_knn** out);
+int tbdk_knn_destroy(tbdk_knn* m);
+/* The next apply starts from an empty model (frames() becomes 0).  The RNG state stays.  No
+ * device work. */
+int tbdk_knn_reset(tbdk_knn* m);
+/* The reference's setters, all at once: takes every field of cfg but the fixed ones, which must
+ * equal the object's (TBDK_EINVAL otherwise, nothing changed), and rng_state, which is ignored.
+ * Holds from the next apply on. */
+int tbdk_knn_set_params(tbdk_knn* m, const tbdk_knn_config* cfg);
+/* apply(frame, fgmask, learningRate): fgmask (device, 8-bit, width x height, mask_pitch bytes a
+ * row) gets 0 (background), shadow_value (shadow) or 255 per pixel, and the model is updated.
+ * The schedule is the reference's, kept on the host: model, indices, next-update planes and the
+ * three counters are zeroed (on the stream; the RNG is not touched) on the first call, after
+ * tbdk_knn_reset and when learning_rate >= 1; the rate is learning_rate if it is >= 0 and this is
+ * not the first frame, else 1 / min(2 * frames, history); the update periods come from the rate
+ * by double log; after the kernel each counter that reached its period is zeroed and its plane
+ * redrawn, in the order short, mid, long.  Asynchronous on `stream`, no allocation, no host
+ * synchronisation; calls on one object are ordered by the caller's stream(s).
+ * TBDK_EINVAL (nothing enqueued, nothing changed): a null pointer, a pitch below a row, and the
+ * learning rates for which the reference converts an infinite, NaN or out-of-range double to int,
+ * which is undefined: NaN, exactly 0, above 1, and a rate so small that a period's quotient
+ * (log(0.1) / log(1 - rate) and its kin) does not fit an int with the increments that follow.
+ * (On a first frame the reference would not look at the given rate; here it is rejected all the
+ * same.)  A rate of exactly 1 is defined: it initialises the model and every quotient is 0.
+ * Timed as "knn_apply", the fills as "knn_randu". */
+int tbdk_knn_apply(tbdk_knn* m, const uint8_t* frame, int pitch, uint8_t* fgmask, int mask_pitch,
+                   double learning_rate, void* stream);
+/* getBackgroundImage: per pixel the first sample, in the order short, mid, long, whose flag is
+ * set (gray: its channel 0), 0 where there is none.  img: device, 8-bit, the frames' channels,
+ * pitch in bytes.  Timed as "knn_background". */
+int tbdk_knn_get_background(tbdk_knn* m, uint8_t* img, int pitch, void* stream);
+/* The model in the reference's layout, for tests and checkpoints (device pointers, any may be
+ * NULL): samples[h][w][3 * nsamples][channels + 1] (uint8), index3[3][h][w] and next3[3][h][w]
+ * (uint8; short, mid, long), counters[3] (int32; short, mid, long) and the RNG state after every
+ * fill enqueued so far (uint64), all tight.  Timed as "knn_model". */
+int tbdk_knn_get_model(tbdk_knn* m, uint8_t* samples, uint8_t* index3, uint8_t* next3, int32_t* counters,
+                       uint64_t* rng_state, void* stream);
+/* frames applied since the model was last cleared */
+int tbdk_knn_frames(tbdk_knn* m, int* nframes);
+
 /* ---- morphology and connected components ----------------------------------- */
 
 /* cv::MorphTypes (the four built) and cv::MorphShapes */

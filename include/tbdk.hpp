@@ -1127,6 +1127,113 @@ inline std::unique_ptr<BackgroundSubtractorMOG2> createBackgroundSubtractorMOG2(
     return std::unique_ptr<BackgroundSubtractorMOG2>(new BackgroundSubtractorMOG2(ctx, history, varThreshold, detectShadows));
 }
 
+// cv::BackgroundSubtractorKNN, the CPU class (video/background_segm.hpp:222-300, video/src/bgfg_KNN.cpp), over
+// tbdk_knn: the model and the RNG stay on the device, apply() only enqueues work.  The model is allocated by the
+// first apply, from the frame's size and channels (8-bit, 1 or 3), which may not change afterwards; so may
+// nSamples not.  rngState is cv::theRNG().state of the thread that would run the reference.  Masks, background
+// images, model, counters and RNG state are the CPU reference's bit for bit.
+class BackgroundSubtractorKNN {
+public:
+    BackgroundSubtractorKNN(Context& ctx, int history = 500, double dist2Threshold = 400.0, bool detectShadows = true,
+                            uint64_t rngState = 0xffffffffull)
+        : ctx_(&ctx)
+    {
+        check(tbdk_knn_config_default(0, 0, 1, &cfg_), "tbdk_knn_config_default");
+        // the reference's constructor keeps its defaults for non-positive arguments (bgfg_KNN.cpp:108,117)
+        if (history > 0) cfg_.history = history;
+        if (dist2Threshold > 0) cfg_.dist2_threshold = (float)dist2Threshold;
+        cfg_.detect_shadows = detectShadows ? 1 : 0;
+        cfg_.rng_state = rngState;
+    }
+    ~BackgroundSubtractorKNN()
+    {
+        if (h_) tbdk_knn_destroy(h_);
+    }
+    BackgroundSubtractorKNN(const BackgroundSubtractorKNN&) = delete;
+    BackgroundSubtractorKNN& operator=(const BackgroundSubtractorKNN&) = delete;
+
+    // image: 8U, 1 or 3 channels; fgmask: 8-bit, the image's size
+    void apply(const GpuMatView& image, const GpuImage& fgmask, double learningRate = -1, void* stream = nullptr)
+    {
+        if (image.depth != DEPTH_8U) throw Error(TBDK_EINVAL, "BackgroundSubtractorKNN::apply: 8-bit frames only");
+        if (!h_) {
+            cfg_.width = image.width, cfg_.height = image.height, cfg_.channels = image.cn;
+            check(tbdk_knn_create(ctx_->get(), &cfg_, &h_), "tbdk_knn_create");
+        }
+        if (image.width != cfg_.width || image.height != cfg_.height || image.cn != cfg_.channels ||
+            fgmask.width != cfg_.width || fgmask.height != cfg_.height)
+            throw Error(TBDK_EINVAL, "BackgroundSubtractorKNN::apply: the frame's size and type may not change");
+        check(tbdk_knn_apply(h_, static_cast<const uint8_t*>(image.data), image.pitch, fgmask.data, fgmask.pitch,
+                             learningRate, stream),
+              "tbdk_knn_apply");
+    }
+    void getBackgroundImage(const GpuMatView& backgroundImage, void* stream = nullptr)
+    {
+        if (!h_ || backgroundImage.width != cfg_.width || backgroundImage.height != cfg_.height ||
+            backgroundImage.depth != DEPTH_8U || backgroundImage.cn != cfg_.channels)
+            throw Error(TBDK_EINVAL, "BackgroundSubtractorKNN::getBackgroundImage: an image of the frames' size and type");
+        check(tbdk_knn_get_background(h_, static_cast<uint8_t*>(backgroundImage.data), backgroundImage.pitch, stream),
+              "tbdk_knn_get_background");
+    }
+    void reset()
+    {
+        if (h_) check(tbdk_knn_reset(h_), "tbdk_knn_reset");
+    }
+    int frames() const
+    {
+        int n = 0;
+        if (h_) check(tbdk_knn_frames(h_, &n), "tbdk_knn_frames");
+        return n;
+    }
+
+    int getHistory() const { return cfg_.history; }
+    void setHistory(int v) { set(&tbdk_knn_config::history, (int32_t)v); }
+    int getNSamples() const { return cfg_.nsamples; }
+    void setNSamples(int v)  // before the first apply only
+    {
+        if (h_ && v != cfg_.nsamples) throw Error(TBDK_EINVAL, "BackgroundSubtractorKNN::setNSamples: model allocated");
+        cfg_.nsamples = v;
+    }
+    double getDist2Threshold() const { return cfg_.dist2_threshold; }
+    void setDist2Threshold(double v) { set(&tbdk_knn_config::dist2_threshold, (float)v); }
+    int getkNNSamples() const { return cfg_.knn_samples; }
+    void setkNNSamples(int v) { set(&tbdk_knn_config::knn_samples, (int32_t)v); }
+    bool getDetectShadows() const { return cfg_.detect_shadows != 0; }
+    void setDetectShadows(bool v) { set(&tbdk_knn_config::detect_shadows, (int32_t)(v ? 1 : 0)); }
+    int getShadowValue() const { return cfg_.shadow_value; }
+    void setShadowValue(int v) { set(&tbdk_knn_config::shadow_value, (int32_t)(v & 255)); }  // narrowed to uchar
+    double getShadowThreshold() const { return cfg_.shadow_threshold; }
+    void setShadowThreshold(double v) { set(&tbdk_knn_config::shadow_threshold, (float)v); }
+    tbdk_knn* get() const { return h_; }
+
+private:
+    template <typename T>
+    void set(T tbdk_knn_config::*field, T v)
+    {
+        const T old = cfg_.*field;
+        cfg_.*field = v;
+        if (!h_) return;
+        const int rc = tbdk_knn_set_params(h_, &cfg_);
+        if (rc != TBDK_OK) {
+            cfg_.*field = old;
+            throw Error(rc, "tbdk_knn_set_params");
+        }
+    }
+    Context* ctx_;
+    tbdk_knn_config cfg_{};
+    tbdk_knn* h_ = nullptr;
+};
+
+// cv::createBackgroundSubtractorKNN(history, dist2Threshold, detectShadows)
+inline std::unique_ptr<BackgroundSubtractorKNN> createBackgroundSubtractorKNN(Context& ctx, int history = 500,
+                                                                              double dist2Threshold = 400.0,
+                                                                              bool detectShadows = true,
+                                                                              uint64_t rngState = 0xffffffffull)
+{
+    return std::unique_ptr<BackgroundSubtractorKNN>(
+        new BackgroundSubtractorKNN(ctx, history, dist2Threshold, detectShadows, rngState));
+}
+
 // ---- morphology and connected components (imgproc/src/morph.dispatch.cpp, connectedcomponents.cpp) over
 // tbdk_morph_u8 / tbdk_connected_components: 8-bit one-channel device images in, everything out stays on the
 // device, nothing synchronises.  Results are the CPU reference's bit for bit, label numbering included.

@@ -166,6 +166,13 @@ class Mog2Config(C.Structure):
                 ("shadow_threshold", C.c_float), ("reserved", C.c_int32)]
 
 
+class KnnConfig(C.Structure):
+    _fields_ = [("width", C.c_int32), ("height", C.c_int32), ("channels", C.c_int32), ("history", C.c_int32),
+                ("nsamples", C.c_int32), ("knn_samples", C.c_int32), ("detect_shadows", C.c_int32),
+                ("shadow_value", C.c_int32), ("dist2_threshold", C.c_float), ("shadow_threshold", C.c_float),
+                ("rng_state", C.c_uint64)]
+
+
 class SubpixParams(C.Structure):
     _fields_ = [("win_w", C.c_int32), ("win_h", C.c_int32), ("zero_w", C.c_int32), ("zero_h", C.c_int32),
                 ("criteria", C.c_int32), ("max_count", C.c_int32), ("epsilon", C.c_double)]
@@ -328,6 +335,16 @@ SIGNATURES = {
     "tbdk_klt_tracker_read": (C.c_int, [C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_int,
                                         C.POINTER(C.c_int), C.POINTER(KltTrackerStats)]),
     "tbdk_klt_tracker_device_state": (C.c_int, [C.c_void_p] + [C.POINTER(C.c_void_p)] * 5),
+    "tbdk_knn_config_default": (C.c_int, [C.c_int, C.c_int, C.c_int, C.POINTER(KnnConfig)]),
+    "tbdk_knn_create": (C.c_int, [C.c_void_p, C.POINTER(KnnConfig), C.POINTER(C.c_void_p)]),
+    "tbdk_knn_destroy": (C.c_int, [C.c_void_p]),
+    "tbdk_knn_reset": (C.c_int, [C.c_void_p]),
+    "tbdk_knn_set_params": (C.c_int, [C.c_void_p, C.POINTER(KnnConfig)]),
+    "tbdk_knn_apply": (C.c_int, [C.c_void_p, C.c_void_p, C.c_int, C.c_void_p, C.c_int, C.c_double, C.c_void_p]),
+    "tbdk_knn_get_background": (C.c_int, [C.c_void_p, C.c_void_p, C.c_int, C.c_void_p]),
+    # m, samples, index3, next3, counters, rng_state, stream
+    "tbdk_knn_get_model": (C.c_int, [C.c_void_p] + [C.c_void_p] * 6),
+    "tbdk_knn_frames": (C.c_int, [C.c_void_p, C.POINTER(C.c_int)]),
     "tbdk_mask_circles_u8": (C.c_int, [C.c_void_p, C.c_void_p, C.c_int, C.c_int, C.c_int, C.c_void_p, C.c_void_p,
                                        C.c_int, C.c_int, C.c_int, C.c_void_p]),
     "tbdk_mog2_config_default": (C.c_int, [C.c_int, C.c_int, C.c_int, C.c_int, C.POINTER(Mog2Config)]),

@@ -21,7 +21,7 @@ child's environment only).  The driver prints checkHardwareSupport; a run whose
 flags do not show the intended state is an error, so a host without AVX2 cannot
 record.  Where the two recordings are byte-identical one copy is stored
 (state "both"); this is asserted for the pyramid, PyrLK, warpAffine, remap,
-warpPerspective, morph and cc.  Where
+warpPerspective, morph, cc and knn.  Where
 they differ, the state the oracle models is stored in full, and for the other
 one: whether the integer-valued results were equal (and those results where
 they were not), the share of equal 32-bit words and the largest absolute
@@ -52,6 +52,7 @@ import _remap_cases as PC  # noqa: E402
 import _homography_cases as HC  # noqa: E402
 import _affine2d_cases as AC  # noqa: E402
 import _mog2_cases as GC  # noqa: E402
+import _knn_cases as KC  # noqa: E402
 import _morph_cases as BC  # noqa: E402
 import _cc_cases as LC  # noqa: E402
 
@@ -62,7 +63,7 @@ MODELLED = {"pyramid": "both", "pyrlk": "both", "warpaffine": "both", "gftt": "n
             "cornermaps": "noavx2", "gftt_f32": "noavx2", "subpix": "both", "gftt_frame": "noavx2",
             "circle": "both", "remap": "both", "warpperspective": "both", "farneback": "noavx2",
             "farneback_box": "noavx2", "hog": "default", "homography": "noavx2", "affine2d": "noavx2", "mog2": "both",
-            "morph": "both", "cc": "both"}
+            "morph": "both", "cc": "both", "knn": "both"}
 
 
 class Driver:
@@ -431,6 +432,32 @@ def rec_mog2(d):
     return cases, {}
 
 
+def rec_knn(d):
+    """BackgroundSubtractorKNN over the sequences of tests/_knn_cases.py, with cv::theRNG() of the calling thread
+    set to the case's seed: every frame's mask and the background images after the marked frames (whole for the
+    base rows, CRC-32s for the others), the update periods of every frame, and theRNG().state after the last
+    frame (two int32 words), which pins the number of steps the fills consumed"""
+    cases = []
+    rows = KC.cases()
+    assert len(rows) == KC.NCASES
+    for case in rows:
+        p, fr = KC.params(case), KC.case_frames(case)
+        n, h, w, cn = case["n"], case["h"], case["w"], case["cn"]
+        want = np.array([t + 1 in case["bg"] for t in range(n)], np.uint8)
+        _, rd = d.run("knn", dict(a=fr, rates=case["rates"].astype(np.float64), bg=want), w=w, h=h, cn=cn, n=n,
+                      seed=p["rng_state"], history=p["history"], nsamples=p["nsamples"], knn=p["knn_samples"],
+                      shadows=p["detect_shadows"], sval=p["shadow_value"], d2t=float(p["dist2_threshold"]),
+                      tau=float(p["shadow_threshold"]))
+        masks = rd("masks", np.uint8).reshape(n, h, w)
+        bgs = rd("bg", np.uint8).reshape((len(case["bg"]),) + fr.shape[1:])
+        ints = dict(masks=KC.stored_masks(case, masks), periods=rd("periods", np.int32).reshape(n, 3),
+                    state=KC.split_state(int(rd("state", np.uint64)[0])))
+        for k, t in enumerate(case["bg"]):
+            ints[f"bg{t}"] = KC.stored_background(case, bgs[k])
+        cases.append((ints, {}))
+    return cases, {}
+
+
 def rec_morph(d):
     """erode / dilate / morphologyEx on the cases of tests/_morph_cases.py, and the getStructuringElement table
     (bit-packed).  The CROSS and ELLIPSE elements the cases use are checked against the reference's own"""
@@ -573,13 +600,13 @@ RECORDERS = {"pyramid": rec_pyramid, "pyrlk": rec_pyrlk, "gftt": rec_gftt, "gftt
              "circle": rec_circle, "warpaffine": rec_warpaffine, "remap": rec_remap,
              "warpperspective": rec_warpperspective, "farneback": rec_farneback, "farneback_box": rec_farneback_box,
              "hog": rec_hog, "homography": rec_homography, "affine2d": rec_affine2d, "mog2": rec_mog2,
-             "morph": rec_morph, "cc": rec_cc}
+             "morph": rec_morph, "cc": rec_cc, "knn": rec_knn}
 # bytes up to which an output is stored whole (tests/_reference_cases.py: WHOLE_LIMIT).  The kernels are
 # compared with the box Farneback flows within a tolerance, so all six stay whole (about 7 KB under LIMIT)
 WHOLE = {"farneback": 20480, "farneback_box": 72800, "pyrlk": 1 << 20, "gftt": 1 << 20, "gftt_mask": 1 << 20,
          "hog": 16384, "subpix": 1 << 20, "gftt_frame": 1 << 20, "remap": PC.WHOLE_LIMIT,
          "warpperspective": PC.WHOLE_LIMIT, "homography": 1 << 20, "affine2d": 1 << 20, "mog2": 1 << 20,
-         "morph": BC.WHOLE_LIMIT, "cc": 1 << 20}
+         "morph": BC.WHOLE_LIMIT, "cc": 1 << 20, "knn": 1 << 20}
 # (gftt_f32: maps above RC.WHOLE_LIMIT as row CRCs; its corner lists are far below it)
 
 
@@ -624,6 +651,8 @@ def case_label(op, i):
         return AC.label(i)
     if op == "mog2":
         return GC.label(i)
+    if op == "knn":
+        return KC.label(i)
     if op == "morph":
         return BC.label(i)
     if op == "cc":

@@ -47,6 +47,16 @@
 //                                                  non-zero byte of bg=): createBackgroundSubtractorMOG2, every
 //                                                  setter, apply(frame, mask, rates[t]) per frame and
 //                                                  getBackgroundImage after the marked ones
+//   knn   a= (n 8-bit frames, raw) w= h= cn= n= rates= (n doubles, raw) bg= (n bytes, raw) seed= (decimal uint64)
+//         history= nsamples= knn= shadows= sval= d2t= tau=
+//                                                  -> masks (n x h x w u8), bg (one image per non-zero byte of bg=),
+//                                                  periods (n x 3 i32), state (1 u64): theRNG().state = seed on the
+//                                                  calling thread, createBackgroundSubtractorKNN, every setter,
+//                                                  apply(frame, mask, rates[t]) per frame, getBackgroundImage after
+//                                                  the marked ones, and theRNG().state after the last frame, which
+//                                                  pins the number of steps the fills consumed; periods are apply()'s
+//                                                  nShortUpdate / nMidUpdate / nLongUpdate expressions evaluated here
+//                                                  with this build's log
 //   morph a= w= h= mop=0..3 [elem= kw= kh=] ax= ay= it= border= bval= inplace=0|1
 //                                                  -> d (u8): erode / dilate (mop 0 / 1) or morphologyEx (mop 2 / 3)
 //                                                  with the element (raw kw x kh bytes; absent: an empty Mat),
@@ -280,6 +290,60 @@ static int run_mog2(const std::string& out)
     return 0;
 }
 
+static int run_knn(const std::string& out)
+{
+    const int w = iarg("w"), h = iarg("h"), cn = iarg("cn"), n = iarg("n");
+    const int type = CV_8UC(cn);
+    Mat all(n * h, w, type);
+    rd(arg("a"), all.data, all.total() * all.elemSize());
+    std::vector<double> rates(n);
+    std::vector<uchar> want(n);
+    rd(arg("rates"), rates.data(), sizeof(double) * n);
+    rd(arg("bg"), want.data(), n);
+    theRNG().state = std::strtoull(arg("seed").c_str(), NULL, 10);
+    const int history = iarg("history"), nN = iarg("nsamples");
+    Ptr<BackgroundSubtractorKNN> m = createBackgroundSubtractorKNN(history, darg("d2t"), iarg("shadows") != 0);
+    m->setHistory(history);
+    m->setNSamples(nN);
+    m->setkNNSamples(iarg("knn"));
+    m->setDist2Threshold(darg("d2t"));
+    m->setDetectShadows(iarg("shadows") != 0);
+    m->setShadowValue(iarg("sval"));
+    m->setShadowThreshold(darg("tau"));
+    Mat masks(n * h, w, CV_8UC1);
+    std::vector<uchar> bgs;
+    std::vector<int> periods;
+    int nframes = 0;
+    for (int t = 0; t < n; ++t) {
+        Mat mask;
+        m->apply(all.rowRange(t * h, (t + 1) * h), mask, rates[t]);
+        if (mask.type() != CV_8UC1 || mask.rows != h || mask.cols != w) throw std::runtime_error("knn: mask type");
+        mask.copyTo(masks.rowRange(t * h, (t + 1) * h));
+        if (nframes == 0 || rates[t] >= 1) nframes = 0;
+        ++nframes;
+        const double rate = rates[t] >= 0 && nframes > 1 ? rates[t] : 1. / std::min(2 * nframes, history);
+        const int Kshort = (int)(log(0.7) / log(1 - rate)) + 1;
+        const int Kmid = (int)(log(0.4) / log(1 - rate)) - Kshort + 1;
+        const int Klong = (int)(log(0.1) / log(1 - rate)) - Kshort - Kmid + 1;
+        periods.push_back(Kshort / nN + 1);
+        periods.push_back(Kmid / nN + 1);
+        periods.push_back(Klong / nN + 1);
+        if (want[t]) {
+            Mat bg;
+            m->getBackgroundImage(bg);
+            if (bg.type() != type || bg.rows != h || bg.cols != w) throw std::runtime_error("knn: background type");
+            Mat c = bg.isContinuous() ? bg : bg.clone();
+            bgs.insert(bgs.end(), c.data, c.data + c.total() * c.elemSize());
+        }
+    }
+    const uint64 state = theRNG().state;
+    wr(out, "masks", masks);
+    wr(out, "bg", bgs.data(), bgs.size());
+    wr(out, "periods", periods.data(), periods.size() * sizeof(int));
+    wr(out, "state", &state, sizeof(state));
+    return 0;
+}
+
 // erode / dilate / morphologyEx, connectedComponentsWithStats, getStructuringElement
 static int run_blobs(const std::string& op, const std::string& out)
 {
@@ -329,6 +393,7 @@ static int run(const std::string& op, const std::string& out)
 {
     if (op == "morph" || op == "cc" || op == "strel") return run_blobs(op, out);
     if (op == "mog2") return run_mog2(out);
+    if (op == "knn") return run_knn(out);
     if (op == "homography") return run_homography(out);
     if (op == "affine2d") return run_affine2d(out);
     const int w = iarg("w"), h = iarg("h"), cn = has("cn") ? iarg("cn") : 1;
