@@ -15,7 +15,19 @@
 //                   the reference's running ColumnSum walked top to bottom ->
 //                   min eigenvalue; per-strip max and the rows' 3x3
 //                   local-maximum ballots (the threshold-independent half of
-//                   the reference's threshold + dilate test)
+//                   the reference's threshold + dilate test).  A wave walks
+//                   its steady rows in straight-line code, four (plane
+//                   kernel: eight) at a time and what is left of them one at
+//                   a time; only the rows at a segment's ends take the
+//                   run-time-flag row.  The ROI's table entry is read through
+//                   the first lane, so row counters, row offsets and the
+//                   buffer descriptors are scalar; the lane's part of a
+//                   store's address is its vector offset, the row's part its
+//                   scalar offset.  Each row's horizontal 3-maximum is taken
+//                   once and carried for the 3x3 test; the strip maximum runs
+//                   as a float maximum (8/16-bit, unmasked).  The row
+//                   arithmetic and the identities behind its spelling:
+//                   gftt_row_math.hpp
 //   2. gftt_select: one 512-thread workgroup per ROI: candidates (local
 //                   maxima above max*q), sort by
 //                   (value desc, address desc) — the reference's deterministic
@@ -38,6 +50,7 @@
 #include <cmath>
 #include <type_traits>
 
+#include "gftt_row_math.hpp"
 #include "klt_gftt_device.hpp"
 #include "tbdk_internal.hpp"
 
@@ -81,29 +94,14 @@ __device__ __forceinline__ float from_right(float v)
     return __int_as_float(__builtin_amdgcn_mov_dpp(__float_as_int(v), 0x130, 0xF, 0xF, true));
 }
 
-// Sobel rows of one image row at columns (x-1, x, x+1) in the reference's
-// filter-engine order (see oracle/gftt_oracle.c): rx = [-1 0 1], ry = [k 2k k]
-struct SobelRow {
-    float rx, ry;
-};
-__device__ __forceinline__ SobelRow sobel_row(float s0, float s1, float s2, float k, float k2)
-{
-    float t = -1.f * s0;
-    t = t + 0.f * s1;
-    t = t + 1.f * s2;
-    float u = k * s0;
-    u = u + k2 * s1;
-    u = u + k * s2;
-    return SobelRow{t, u};
-}
-// ... of a 32F image (TBDK_PIX_F32; a 16U image is one converted in the load):
-// the reference's float row filter for ksize 3, SymmRowSmallFilter<float, float>
-// (filter.simd.hpp:1708-1743, 2425-2469) in its unfused form: rx = S[x+1] - S[x-1],
-// ry = S[x]*k0 + (S[x-1] + S[x+1])*k1
-__device__ __forceinline__ SobelRow sobel_row_f32(float s0, float s1, float s2, float k, float k2)
-{
-    return SobelRow{s2 - s0, s1 * k2 + (s0 + s2) * k};
-}
+// h(v) = max(v, left neighbour's v, right neighbour's v): two DPP moves and one
+// v_max3_f32 (the end lanes' missing neighbour reads 0 as above; they are never
+// output lanes).  For values that are never NaN the maximum is exact.
+__device__ __forceinline__ float hmax3(float v) { return fmaxf(fmaxf(v, from_left(v)), from_right(v)); }
+
+// The Sobel row terms (sobel_row, sobel_row_f32), the gradient pair (grad_lit,
+// grad_int) and the min eigenvalue (min_eig): gftt_row_math.hpp, shared with the
+// host check of the identities their shorter spellings rest on.
 
 // Fused Sobel -> cov -> boxFilter -> min eigenvalue for one 56-column strip of
 // a ROI per workgroup.  Lane L holds ROI column x0 - 4 + L (lanes 4..59 produce
@@ -134,6 +132,8 @@ constexpr int kEigWaves = TBDK_GFTT_EIG_WAVES;  // row segments (waves) per stri
 constexpr int kEigPref = 8;   // pixel rows in flight per wave (the eigenvalue-plane kernel)
 // ... in the compact-candidate kernel: 4 keeps it at <= 128 VGPRs (8: 148),
 // so its waves fit where one of the loop's PyrLK waves (121) has ended
+// (chosen when the walk's row bookkeeping sat in vector registers: 127 VGPRs at
+// 4; it holds 80 since, and 8 has not been measured again)
 #ifndef TBDK_GFTT_EIG_PREF_C
 #define TBDK_GFTT_EIG_PREF_C 4
 #endif
@@ -199,12 +199,16 @@ __device__ __forceinline__ SobelRow eig_srow(const EigLane& g, float v)
     else return sobel_row(g.mir ? rr : l, v, g.mir ? l : rr, g.k, g.k2);
 }
 
-// the three cov channels of one row and their boxFilter row sums ((l + c) + r in double)
+// the three cov channels of one row and their boxFilter row sums ((l + c) + r in double).
+// The gradient pair's closing "+ 0" is spelled only where a -0 can meet it, on
+// 32F images (a caller's -0 pixel); on 8-bit and 16-bit pixels it cannot change a
+// bit (grad_int, gftt_row_math.hpp)
+template <int PX = TBDK_PIX_U8>
 __device__ __forceinline__ void eig_rowsums(const EigLane& g, const SobelRow& p, const SobelRow& c,
                                             const SobelRow& n, double (&out)[3])
 {
-    const float dx = (p.rx + n.rx) * g.k + (c.rx * g.k2 + 0.f);
-    const float dy = (n.ry - p.ry) + 0.f;
+    const Grad gr = PX == TBDK_PIX_F32 ? grad_lit(p, c, n, g.k, g.k2) : grad_int(p, c, n, g.k, g.k2);
+    const float dx = gr.dx, dy = gr.dy;
     const float cv[3] = {dx * dx, dx * dy, dy * dy};
 #pragma unroll
     for (int ch = 0; ch < 3; ++ch) {
@@ -241,30 +245,54 @@ __device__ __forceinline__ void eig_segment(const EigLane& g, const EigMask& gm,
     double qa[3], qb[3];  // rs(y - 1), rs(y)
     {
         const int rm = refl(ys - 1, H);  // the box filter reflects cov rows
-        eig_rowsums(g, eig_srow<PX>(g, pix(rm - 1)), eig_srow<PX>(g, pix(rm)), eig_srow<PX>(g, pix(rm + 1)), qa);
+        eig_rowsums<PX>(g, eig_srow<PX>(g, pix(rm - 1)), eig_srow<PX>(g, pix(rm)), eig_srow<PX>(g, pix(rm + 1)), qa);
     }
     SobelRow wa = eig_srow<PX>(g, pix(ys)), wb = eig_srow<PX>(g, pix(ys + 1));
-    eig_rowsums(g, eig_srow<PX>(g, pix(ys - 1)), wa, wb, qb);
+    eig_rowsums<PX>(g, eig_srow<PX>(g, pix(ys - 1)), wa, wb, qb);
     if (fresh) {
 #pragma unroll
         for (int ch = 0; ch < 3; ++ch) S[ch] = (0.0 + qa[ch]) + qb[ch];
     }
 #pragma unroll
     for (int ch = 0; ch < 3; ++ch) S0[ch] = S[ch];
+    // Row y - 1's local-maximum test, e1 >= its 8 neighbours, from the rows'
+    // horizontal maxima h(v) = max(v, l(v), r(v)) (hmax3), each taken once as
+    // its row is produced and carried with it: e1 >= max3(h(e2), h(e1), h(e)).
+    // The same predicate as the test against the 8 neighbours alone, because
+    // e1 >= e1 and max is exact — for values that are never NaN, which holds on
+    // 8-bit and 16-bit pixels (min_eig, gftt_row_math.hpp).  A 32F image can
+    // bring NaN (inf - inf in min_eig), and with all 8 neighbours NaN the
+    // 8-neighbour maximum is NaN (test false) where the 9-value one would be e1
+    // (test true): those instances keep the 8-neighbour form.
+    constexpr bool HLM = PX != TBDK_PIX_F32;
+    // The strip maximum: a float maximum through the rows, its key taken once
+    // at the end of the segment, in the unmasked 8-bit and 16-bit instances.
+    // fkey is monotonic and e is there finite and never -0 (min_eig), so the
+    // key of the maximum is the maximum of the keys.  It runs on every lane
+    // (one v_max_f32 per row): the lanes that are not output lanes are left out
+    // where the key is taken.  Masked and 32F instances keep the keys.
+    constexpr bool FBEST = !masked && PX != TBDK_PIX_F32;
     float e1 = 0.f, e2 = 0.f;  // eigenvalues of rows y - 1, y - 2
+    float h1 = 0.f, h2 = 0.f;  // ... and their horizontal maxima (HLM)
+    float bestf = -INFINITY;   // FBEST
     // E and lm through buffer stores: a lane that must not write gets an offset
     // past the buffer, which the hardware drops, so the steady rows below stay
-    // one straight-line block (no exec-mask branches between rows)
+    // one straight-line block (no exec-mask branches between rows).  The lane's
+    // part of an offset (its column, or kDrop) is the store's vector offset and
+    // the row's part its scalar offset, so no per-row vector add or select forms
+    // the address; a dropped lane's kDrop plus a row offset stays past the buffer
+    // (both are far below 2^31).
     const __amdgpu_buffer_rsrc_t rE =
-        __builtin_amdgcn_make_buffer_rsrc(E - g.x, (short)0, ep * H * 4, 0x00020000);
+        __builtin_amdgcn_make_buffer_rsrc(E, (short)0, ep * H * 4, 0x00020000);
     const __amdgpu_buffer_rsrc_t rL = __builtin_amdgcn_make_buffer_rsrc(lm, (short)0, lm ? H * 8 : 0, 0x00020000);
     constexpr uint32_t kDrop = 0x80000000u;
     const uint32_t eoff = g.out_lane ? (uint32_t)g.x * 4u : kDrop;
+    const uint32_t loff = lane == 0 ? 0u : kDrop;
     // one walked row y (cur = pixel row y + 2); the flags are compile-time true
     // in the steady rows
     auto row = [&](auto steady, int y, float cur, bool has_next, bool store, bool lmx) {
         constexpr bool ST = decltype(steady)::value;
-        bool m_in = true;  // row y's mask byte (in flight across the row's arithmetic)
+        [[maybe_unused]] bool m_in = true;  // row y's mask byte (in flight across the row's arithmetic)
         if constexpr (masked) {
             if (ST || store) m_in = eig_mask_ld(gm, y);
         }
@@ -272,7 +300,7 @@ __device__ __forceinline__ void eig_segment(const EigLane& g, const EigMask& gm,
         SobelRow wc = wb;
         if (ST || has_next) {  // entering cov row y + 1 (image rows y, y+1, y+2)
             wc = eig_srow<PX>(g, cur);
-            eig_rowsums(g, wa, wb, wc, in);
+            eig_rowsums<PX>(g, wa, wb, wc, in);
         } else {  // rs(refl(H)) == rs(H - 2) == rs(y - 1)
 #pragma unroll
             for (int ch = 0; ch < 3; ++ch) in[ch] = qa[ch];
@@ -288,35 +316,45 @@ __device__ __forceinline__ void eig_segment(const EigLane& g, const EigMask& gm,
         }
         wa = wb;
         wb = wc;
-        const float aa = box[0] * 0.5f, bb = box[1], cc = box[2] * 0.5f;
-        const float t = aa - cc;
-        const float e = (aa + cc) - sqrtf(bb * bb + t * t);
+        const float e = min_eig(box[0], box[1], box[2]);
         if (ST || store) {
-            if constexpr (!compact)
-                __builtin_amdgcn_raw_buffer_store_b32(__float_as_uint(e), rE, eoff == kDrop ? kDrop : eoff + (uint32_t)(y * ep * 4), 0, 0);
-            const int kk = fkey(e);
-            if constexpr (masked) best = (g.out_lane && m_in && kk > best) ? kk : best;
-            else best = (g.out_lane && kk > best) ? kk : best;
+            if constexpr (!compact) __builtin_amdgcn_raw_buffer_store_b32(__float_as_uint(e), rE, eoff, y * ep * 4, 0);
+            if constexpr (FBEST) {
+                bestf = fmaxf(bestf, e);
+            } else {
+                const int kk = fkey(e);
+                if constexpr (masked) best = (g.out_lane && m_in && kk > best) ? kk : best;
+                else best = (g.out_lane && kk > best) ? kk : best;
+            }
         }
+        float h = 0.f;
+        if constexpr (HLM) h = hmax3(e);
         if (ST || lmx) {  // row y - 1's 3x3 neighbourhood is now complete
-            float m = fmaxf(e2, e);
-            m = fmaxf(m, fmaxf(from_left(e2), from_right(e2)));
-            m = fmaxf(m, fmaxf(from_left(e1), from_right(e1)));
-            m = fmaxf(m, fmaxf(from_left(e), from_right(e)));
+            float m;
+            if constexpr (HLM) {
+                m = fmaxf(fmaxf(h2, h1), h);
+            } else {
+                m = fmaxf(e2, e);
+                m = fmaxf(m, fmaxf(from_left(e2), from_right(e2)));
+                m = fmaxf(m, fmaxf(from_left(e1), from_right(e1)));
+                m = fmaxf(m, fmaxf(from_left(e), from_right(e)));
+            }
             const bool lmax = x_in && e1 >= m;
             const uint64_t bal = __ballot(lmax);
             typedef unsigned int u32x2 __attribute__((ext_vector_type(2)));
             const u32x2 bv = {(unsigned)bal, (unsigned)(bal >> 32)};
-            __builtin_amdgcn_raw_buffer_store_b64(bv, rL, lane == 0 ? (uint32_t)((y - 1) * 8) : kDrop, 0, 0);
+            __builtin_amdgcn_raw_buffer_store_b64(bv, rL, loff, (y - 1) * 8, 0);
             if constexpr (compact) {  // row y - 1's candidates, packed in lane order
                 const uint32_t rk =
                     __builtin_amdgcn_mbcnt_hi((unsigned)(bal >> 32), __builtin_amdgcn_mbcnt_lo((unsigned)bal, 0u));
-                __builtin_amdgcn_raw_buffer_store_b32(__float_as_uint(e1), rE,
-                                                      lmax ? (uint32_t)(((y - 1) * ep + ccol + (int)rk) * 4) : kDrop, 0, 0);
+                __builtin_amdgcn_raw_buffer_store_b32(__float_as_uint(e1), rE, lmax ? rk * 4u : kDrop,
+                                                      ((y - 1) * ep + ccol) * 4, 0);
             }
         }
         e2 = e1;
         e1 = e;
+        h2 = h1;
+        h1 = h;
     };
     // any row, flags at run time (the capture of Scap before row ycap included)
     auto generic = [&](int y) {
@@ -329,16 +367,20 @@ __device__ __forceinline__ void eig_segment(const EigLane& g, const EigMask& gm,
             yc >= y0 && yc < y1 && yc >= 1 && yc <= H - 2);
     };
     // steady rows [sa, sb): own rows with a complete 3x3 row above, a next row,
-    // and not the capture row; the rest of [ys, ye) by generic rows
+    // and not the capture row, all by the straight-line row: PREF at a time
+    // while that many are left, then one at a time (the up to PREF - 1 rows left
+    // over, or every steady row of a segment with fewer than PREF), the next
+    // row's pixel in flight.  Generic rows are what is left of [ys, ye): the rows
+    // before sa, the capture row, the last row and the halo row after it.
     const int sa = max(max(y0 + 1, 2), ys);
     int sb = min(min(y1, H - 1), ye);
     if (ycap >= 0) sb = min(sb, ycap);
     int y = ys;
-    if (sb - sa >= PREF) {
+    if (sb > sa) {
         for (; y < sa; ++y) generic(y);
         float nxt[PREF];
 #pragma unroll
-        for (int j = 0; j < PREF; ++j) nxt[j] = pix_fwd(y + 2 + j);
+        for (int j = 0; j < PREF; ++j) nxt[j] = pix_fwd(min(y + 2 + j, H));
         for (; y + PREF <= sb; y += PREF) {
             float cur[PREF];
 #pragma unroll
@@ -348,8 +390,20 @@ __device__ __forceinline__ void eig_segment(const EigLane& g, const EigMask& gm,
 #pragma unroll
             for (int j = 0; j < PREF; ++j) row(std::true_type{}, y + j, cur[j], true, true, true);
         }
+        float cur = nxt[0];
+        for (; y < sb; ++y) {
+            const float nx = pix_fwd(min(y + 3, H));  // in flight
+            row(std::true_type{}, y, cur, true, true, true);
+            cur = nx;
+        }
     }
     for (; y < ye; ++y) generic(y);
+    if constexpr (FBEST) {
+        // a live segment has stored at least one row, so an output lane's
+        // maximum is a finite eigenvalue here
+        const int kk = fkey(bestf);
+        best = (g.out_lane && kk > best) ? kk : best;
+    }
 }
 
 // compact (GfttArgs::compact, see eig_segment): one instantiation per mode,
@@ -364,7 +418,17 @@ __device__ __forceinline__ void gftt_eig_body(const GfttArgs& a)
     __shared__ int s_best[kEigWaves];
     __shared__ int s_bad;
     const int r = roi_of_cblock(a, blockIdx.x);
-    const GfttRoi R = roi_at(a, r);
+    // The ROI's entry is the same in every lane, but the compiler does not see it
+    // (the table indexed in the kernel arguments reads as per-lane data), and with
+    // it every row index, row count and buffer descriptor below was per-lane data
+    // too: each buffer load and store of the walk ran in a loop over the distinct
+    // descriptors among the lanes (five v_readfirstlane and three compares per
+    // access, about 35 vector instructions per steady row), and the row counters
+    // and offsets in vector registers.  Read from the first lane, the entry is
+    // scalar, and so is all that follows from it.  The values are unchanged.
+    const GfttRoi Rv = roi_at(a, r);
+    auto uni = [](int v) { return __builtin_amdgcn_readfirstlane(v); };
+    const GfttRoi R{uni(Rv.x), uni(Rv.y), uni(Rv.w), uni(Rv.h), uni(Rv.off), uni(Rv.moff), uni(Rv.cblk)};
     const int wv = __builtin_amdgcn_readfirstlane(threadIdx.x >> 6);
     const int lane = threadIdx.x & 63;
     const int H = R.h;
@@ -412,7 +476,7 @@ __device__ __forceinline__ void gftt_eig_body(const GfttArgs& a)
         gm.col = g.out_lane ? (uint32_t)g.x : 0xFFFFFFFFu;  // past a buffer of any accepted size (< 2^32 bytes)
         gm.pitch = a.mask_pitch;
     }
-    float* E = a.eig + R.off + g.x;
+    float* E = a.eig + R.off;  // the ROI's eigenvalue plane (the same in every lane)
     // local-maximum words of this strip (ROIs of at least 3x3; never written otherwise)
     uint64_t* lm = a.lmax + R.moff + (size_t)strip * H;
     const bool has_lm = R.w >= 3 && H >= 3;
@@ -473,8 +537,17 @@ __device__ __forceinline__ void gftt_eig_body(const GfttArgs& a)
         __syncthreads();  // s_cap is rewritten below
         if (wv >= bad && live) {
             best = INT_MIN;
-            eig_segment<compact, masked, kPref, PX>(g, gm, E, has_lm ? lm : nullptr, R.w, gftt_epitch(R.w), y0, y1, ys,
-                                                    ye, ycap, false, S, S0, Scap, best, ccol);
+            // the segment's rows again, from a first row the compiler cannot see
+            // through: otherwise everything the walk derives from them before
+            // its first row (flags, row offsets) is hoisted out of this loop as
+            // loop invariant and held in scalar registers across it, more than
+            // there are
+            int c0 = y0;
+            asm volatile("" : "+s"(c0));
+            const int c1 = min(H, c0 + L);
+            eig_segment<compact, masked, kPref, PX>(g, gm, E, has_lm ? lm : nullptr, R.w, gftt_epitch(R.w), c0, c1,
+                                                    c0 > 0 ? c0 - 1 : 0, min(H, c1 + 1), c1 < H ? c1 - 1 : -1, false, S,
+                                                    S0, Scap, best, ccol);
             if (ycap >= 0) {
 #pragma unroll
                 for (int ch = 0; ch < 3; ++ch) s_cap[wv][ch][lane] = Scap[ch];
