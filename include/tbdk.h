@@ -112,6 +112,10 @@ int tbdk_ctx_destroy(tbdk_ctx* ctx);
  *       one workgroup's LDS where its candidates and accepted corners fit, and
  *       by the wide path (candidates and accepted state in global scratch)
  *       where they do not; 1: every ROI by the wide path (results equal).
+ *   "blur_generic" (0/1, default 0): tbdk_gaussian_blur_u8: 1 runs every kernel
+ *       size through the instance that takes its sizes at run time; 0: square
+ *       kernels of 3, 5, 7 and 11 through their compile-time instances
+ *       (results equal).
  *   "pyr_fuse" (0/1, default 1): tbdk_pyr_build of a u8 pyramid: 1
  *       computes level 0's padded copy and level 1 in one launch, then one
  *       launch per level; 0: one launch per level
@@ -1822,6 +1826,86 @@ int tbdk_morph_u8(tbdk_ctx* ctx, int op, const uint8_t* src, int width, int heig
 int tbdk_connected_components(tbdk_ctx* ctx, const uint8_t* img, int width, int height, int pitch, int32_t* labels,
                               int labels_pitch, int connectivity, int ccltype, int32_t* stats, double* centroids,
                               int cap, int32_t* n_labels, void* stream);
+
+/* ---- GaussianBlur (8-bit, fixed point) and threshold ------------------------ */
+
+/* cv::ThresholdTypes */
+#define TBDK_THRESH_BINARY 0
+#define TBDK_THRESH_BINARY_INV 1
+#define TBDK_THRESH_TRUNC 2
+#define TBDK_THRESH_TOZERO 3
+#define TBDK_THRESH_TOZERO_INV 4
+#define TBDK_THRESH_MASK 7
+#define TBDK_THRESH_OTSU 8
+#define TBDK_THRESH_TRIANGLE 16 /* not built */
+
+/* The n 8.8 fixed-point coefficients cv::GaussianBlur uses on 8-bit images
+ * (getFixedpointGaussianKernel<ufixedpoint16>, imgproc/src/smooth.dispatch.cpp:124-169), host only:
+ * the literal tables for n = 1, 3, 5, 7 at sigma <= 0, otherwise exp(-x^2 / (2 sigma^2)) normalised
+ * and rounded to 1/256 in the reference's softdouble arithmetic, its own exp included; sigma <= 0 is
+ * 0.15 n + 0.35.  They need not sum to 256.  TBDK_EINVAL: n < 1, out NULL. */
+int tbdk_gaussian_kernel_u8(int n, double sigma, uint16_t* out);
+
+/* The threshold stage tbdk_gaussian_blur_u8 can apply to every output byte before it is stored:
+ * cv::threshold(blurred, dst, thresh, maxval, type) with one of the five plain types. */
+typedef struct tbdk_thresh_params {
+    double thresh, maxval;
+    int32_t type;
+    int32_t reserved;
+} tbdk_thresh_params;
+
+/* cv::GaussianBlur(src, dst, Size(kw, kh), sigma_x, sigma_y, border_type | BORDER_ISOLATED) on an
+ * 8-bit device image of cn = 1, 3 or 4 interleaved channels, 1..65535 a side, pitched, any
+ * alignment; every output byte is the reference's (GaussianBlurFixedPoint, imgproc/src/smooth.simd.hpp):
+ * a row pass H = min(65535, sum kx[i] s[i]) in 8.8 fixed point, a column pass
+ * min(255, (sum ky[j] H[j] + 32768) >> 16), terms outside the image fetched by borderInterpolate, or
+ * left out under BORDER_CONSTANT.
+ *   kw, kh   : odd, 1..31; <= 0 with a positive sigma is the reference's automatic size for 8-bit
+ *              images, cvRound(6 sigma + 1) | 1; sigma_y <= 0 means sigma_x; a one-row or one-column
+ *              image under a border other than CONSTANT collapses that dimension to 1; 1 x 1 copies
+ *   border_type : TBDK_BORDER_CONSTANT (zero), _REPLICATE, _REFLECT, _WRAP or _REFLECT_101, for
+ *              images smaller than the kernel too
+ *   fused    : NULL, or the threshold applied to every output byte: the result is that of
+ *              tbdk_threshold on the blurred image, with no intermediate image
+ * One launch: a workgroup stages its source tile and halo in LDS, writes the row pass there as
+ * 16-bit words and reads the column pass from them; the coefficients travel in the kernel
+ * arguments.  Where src and dst overlap the blur goes to the context's intermediate plane
+ * (tbdk_morph_u8's; calls on one context are ordered by the caller) and is copied out by a second
+ * launch, as the reference clones its source.  Enqueues on `stream` and returns: no upload, no host
+ * synchronisation, no allocation unless that plane has to grow.  TBDK_EINVAL, with nothing enqueued
+ * and dst untouched: a null image, cn other than 1, 3, 4, a size outside 1..65535, a pitch below a
+ * row, BORDER_TRANSPARENT or an unknown border, an even size, a size above 31 (given or automatic),
+ * a size <= 0 without a positive sigma, a NaN sigma, a fused type other than the five plain ones
+ * (THRESH_OTSU needs the whole blurred image first).  Timed as "blur". */
+int tbdk_gaussian_blur_u8(tbdk_ctx* ctx, const uint8_t* src, int width, int height, int cn, int src_pitch,
+                          uint8_t* dst, int dst_pitch, int kw, int kh, double sigma_x, double sigma_y,
+                          int border_type, const tbdk_thresh_params* fused, void* stream);
+
+/* cv::threshold(src, dst, thresh, maxval, type) on a device image, pitched (bytes), any alignment for
+ * 8-bit images; src == dst is allowed.
+ *   pix      : TBDK_PIX_U8 with any cn >= 1 (the image is width * cn bytes a row), or TBDK_PIX_F32
+ *              with cn >= 1 (pointers and pitches multiples of 4)
+ *   8-bit    : thresh.cpp:1556-1585: the threshold is cvFloor(thresh), maxval
+ *              saturate_cast<uchar>(cvRound(maxval)), for TRUNC the threshold; thresholds below 0 and
+ *              from 255 on give the reference's constant fills and copies
+ *   32F      : the comparisons of the reference's vector body, in float: a NaN pixel is neither above
+ *              nor at-or-below the threshold, and TRUNC returns the threshold for it (the reference's
+ *              scalar remainder, the last w h mod 8 elements of a continuous image, returns the NaN)
+ *   type     : one of the five, or with TBDK_THRESH_OTSU on a one-channel 8-bit image: a device
+ *              histogram, getThreshVal_Otsu_8u's scan over it in double on one lane, in the
+ *              reference's operation order, and an apply pass that reads the threshold on the
+ *              device; thresh is ignored
+ *   thresh_used : optional host double: the value the reference returns (the floored threshold for
+ *              8-bit images); NaN with OTSU, whose value exists only on the device
+ *   otsu_dev : required with OTSU, ignored otherwise: a device int32 that receives the chosen
+ *              threshold, in stream order
+ * Enqueues on `stream` and returns: no host synchronisation; OTSU uses 1 KB of the context's
+ * intermediate plane.  TBDK_EINVAL, nothing enqueued: a null image, another pix, a size below 1 or
+ * above 65535 a side, a pitch below a row, THRESH_TRIANGLE or an unknown type, OTSU on anything but
+ * one-channel 8-bit or without otsu_dev, a NaN thresh or maxval.  Timed as "threshold". */
+int tbdk_threshold(tbdk_ctx* ctx, const void* src, int pix, int width, int height, int cn, int src_pitch, void* dst,
+                   int dst_pitch, double thresh, double maxval, int type, double* thresh_used, int32_t* otsu_dev,
+                   void* stream);
 
 /* ---- synthetic sequences (bench / test input) ----------------------------- */
 

@@ -1323,6 +1323,68 @@ inline void connectedComponentsWithStats(Context& ctx, const GpuImage& image, co
           "tbdk_connected_components");
 }
 
+// ---- GaussianBlur on 8-bit images and threshold (imgproc/src/smooth.dispatch.cpp, smooth.simd.hpp, thresh.cpp)
+// over tbdk_gaussian_blur_u8 / tbdk_threshold.  Results are the CPU reference's bit for bit; nothing synchronises.
+enum ThresholdTypes {
+    THRESH_BINARY = 0, THRESH_BINARY_INV = 1, THRESH_TRUNC = 2, THRESH_TOZERO = 3, THRESH_TOZERO_INV = 4, THRESH_OTSU = 8
+};
+
+// the threshold stage GaussianBlur can fuse in: cv::threshold(blurred, dst, thresh, maxval, type), a plain type
+struct FusedThreshold {
+    double thresh = 0, maxval = 255;
+    int type = THRESH_BINARY;
+};
+
+// getFixedpointGaussianKernel<ufixedpoint16>(n, sigma): the 8.8 coefficients the 8-bit blur uses
+inline std::vector<uint16_t> getGaussianKernelU8(int n, double sigma)
+{
+    if (n < 1) throw Error(TBDK_EINVAL, "getGaussianKernelU8");
+    std::vector<uint16_t> k((size_t)n);
+    check(tbdk_gaussian_kernel_u8(n, sigma, k.data()), "tbdk_gaussian_kernel_u8");
+    return k;
+}
+
+// cv::GaussianBlur(src, dst, ksize, sigmaX, sigmaY, borderType | BORDER_ISOLATED) on CV_8UC1 / 8UC3 / 8UC4 views;
+// dst may be src.  fused: applied to every output byte in the same launch
+inline void GaussianBlur(Context& ctx, const GpuMatView& src, const GpuMatView& dst, Size ksize, double sigmaX,
+                         double sigmaY = 0, int borderType = TBDK_BORDER_REFLECT_101, void* stream = nullptr,
+                         const FusedThreshold* fused = nullptr)
+{
+    if (src.depth != DEPTH_8U || dst.depth != DEPTH_8U || src.width != dst.width || src.height != dst.height ||
+        src.cn != dst.cn)
+        throw Error(TBDK_EINVAL, "GaussianBlur: 8-bit views of one size and channel count expected");
+    tbdk_thresh_params t{0, 0, 0, 0};
+    if (fused) t = tbdk_thresh_params{fused->thresh, fused->maxval, fused->type, 0};
+    check(tbdk_gaussian_blur_u8(ctx.get(), static_cast<const uint8_t*>(src.data), src.width, src.height, src.cn,
+                                src.pitch, static_cast<uint8_t*>(dst.data), dst.pitch, ksize.width, ksize.height, sigmaX,
+                                sigmaY, borderType, fused ? &t : nullptr, stream),
+          "tbdk_gaussian_blur_u8");
+}
+inline void GaussianBlur(Context& ctx, const GpuImage& src, const GpuImage& dst, Size ksize, double sigmaX,
+                         double sigmaY = 0, int borderType = TBDK_BORDER_REFLECT_101, void* stream = nullptr,
+                         const FusedThreshold* fused = nullptr)
+{
+    GaussianBlur(ctx, GpuMatView{src.data, src.width, src.height, src.pitch, DEPTH_8U, 1},
+                 GpuMatView{dst.data, dst.width, dst.height, dst.pitch, DEPTH_8U, 1}, ksize, sigmaX, sigmaY, borderType,
+                 stream, fused);
+}
+
+// cv::threshold(src, dst, thresh, maxval, type) on 8-bit views of any channel count and CV_32F views; returns
+// what the reference returns.  With THRESH_OTSU (CV_8UC1) the value exists only on the device: otsu (a device
+// int32) receives it in stream order and the return value is NaN
+inline double threshold(Context& ctx, const GpuMatView& src, const GpuMatView& dst, double thresh, double maxval,
+                        int type, void* stream = nullptr, int32_t* otsu = nullptr)
+{
+    if (src.depth != dst.depth || (src.depth != DEPTH_8U && src.depth != DEPTH_32F) || src.width != dst.width ||
+        src.height != dst.height || src.cn != dst.cn)
+        throw Error(TBDK_EINVAL, "threshold: 8-bit or 32F views of one size and channel count expected");
+    double used = 0;
+    check(tbdk_threshold(ctx.get(), src.data, src.depth == DEPTH_8U ? TBDK_PIX_U8 : TBDK_PIX_F32, src.width, src.height,
+                         src.cn, src.pitch, dst.data, dst.pitch, thresh, maxval, type, &used, otsu, stream),
+          "tbdk_threshold");
+    return used;
+}
+
 // The sample's whole per-frame path (samples/gpu/tbd.cpp:568-622) on a TbdLoop:
 // colour frame -> cvtColor -> optional resize -> HOG detectMultiScale -> the
 // loop (tbdk_tbd_step_image).  `loop` and `ctx` must outlive it.

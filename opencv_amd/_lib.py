@@ -72,6 +72,10 @@ class LkParams(C.Structure):
     ]
 
 
+class ThreshParams(C.Structure):
+    _fields_ = [("thresh", C.c_double), ("maxval", C.c_double), ("type", C.c_int32), ("reserved", C.c_int32)]
+
+
 class Roi(C.Structure):
     _fields_ = [("x", C.c_int32), ("y", C.c_int32), ("width", C.c_int32), ("height", C.c_int32)]
 
@@ -360,6 +364,15 @@ SIGNATURES = {
     # ctx, op, src, w, h, spitch, dst, dpitch, element, kw, kh, ax, ay, iterations, border, border value, stream
     "tbdk_morph_u8": (C.c_int, [C.c_void_p, C.c_int, C.c_void_p, C.c_int, C.c_int, C.c_int, C.c_void_p, C.c_int,
                                 C.c_void_p, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, C.c_void_p]),
+    "tbdk_gaussian_kernel_u8": (C.c_int, [C.c_int, C.c_double, C.c_void_p]),
+    # ctx, src, w, h, cn, spitch, dst, dpitch, kw, kh, sigma x, sigma y, border, fused threshold, stream
+    "tbdk_gaussian_blur_u8": (C.c_int, [C.c_void_p, C.c_void_p, C.c_int, C.c_int, C.c_int, C.c_int, C.c_void_p,
+                                        C.c_int, C.c_int, C.c_int, C.c_double, C.c_double, C.c_int,
+                                        C.POINTER(ThreshParams), C.c_void_p]),
+    # ctx, src, pix, w, h, cn, spitch, dst, dpitch, thresh, maxval, type, thresh used (host), otsu word (device), stream
+    "tbdk_threshold": (C.c_int, [C.c_void_p, C.c_void_p, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, C.c_void_p,
+                                 C.c_int, C.c_double, C.c_double, C.c_int, C.POINTER(C.c_double), C.c_void_p,
+                                 C.c_void_p]),
     # ctx, img, w, h, pitch, labels, labels pitch, connectivity, ccltype, stats, centroids, cap, n_labels, stream
     "tbdk_connected_components": (C.c_int, [C.c_void_p, C.c_void_p, C.c_int, C.c_int, C.c_int, C.c_void_p, C.c_int,
                                             C.c_int, C.c_int, C.c_void_p, C.c_void_p, C.c_int, C.c_void_p,

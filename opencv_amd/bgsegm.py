@@ -373,3 +373,14 @@ def detections_from_stats(stats: torch.Tensor, n_labels, min_area: int = 1, max_
     out["x"], out["y"], out["width"], out["height"] = rows[:, 0], rows[:, 1], rows[:, 2], rows[:, 3]
     out["confidence"] = 1.0
     return out
+
+
+def smooth_mask(mask: torch.Tensor, ksize=(11, 11), sigma: float = 3.5, thresh: float = 10, dst: torch.Tensor | None = None,
+                stream=None, ctx: Context | None = None) -> torch.Tensor:
+    """samples/cpp/bgfg_segm.cpp's smoothMask step, GaussianBlur(mask, mask, Size(11, 11), 3.5, 3.5) followed by
+    threshold(mask, mask, 10, 255, THRESH_BINARY), as one launch with no intermediate image; every byte is what
+    the two reference calls give.  dst None: a new tensor (pass the mask itself for the sample's in-place form)."""
+    from . import imgproc
+
+    return imgproc.gaussian_blur(mask, ksize, sigma, dst, sigma, imgproc.BORDER_REFLECT_101, stream,
+                                 (thresh, 255, imgproc.THRESH_BINARY), ctx)

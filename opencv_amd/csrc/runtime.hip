@@ -205,6 +205,11 @@ int tbdk_ctx_set_option(tbdk_ctx* ctx, const char* name, int64_t value)
         ctx->gftt.fill = (int)value;
         return TBDK_OK;
     }
+    if (std::strcmp(name, "blur_generic") == 0) {
+        if (value < 0 || value > 1) return TBDK_EINVAL;
+        ctx->opt_blur_generic = (int)value;
+        return TBDK_OK;
+    }
     if (std::strcmp(name, "gftt_wide") == 0) {
         if (value < 0 || value > 1) return TBDK_EINVAL;
         ctx->opt_gftt_wide = (int)value;

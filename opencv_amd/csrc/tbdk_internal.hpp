@@ -117,6 +117,7 @@ struct tbdk_ctx {
     int opt_tbd_subpix = 0;      // tbdk_ctx_set_option("tbd_subpix"): the loop refines its GFTT corners, window half size, 0 = off (read by tbdk_tbd_create)
     int opt_alloc_fill = -1;     // tbdk_ctx_set_option("alloc_fill"): test aid, every new device allocation filled with this byte (-1: off)
     int opt_gftt_wide = 0;       // tbdk_ctx_set_option("gftt_wide"): 0 = the wide selection where the LDS one cannot serve, 1 = for every ROI
+    int opt_blur_generic = 0;    // tbdk_ctx_set_option("blur_generic"): 1 = the run-time-size instance of the blur kernel for every size (a test aid)
     std::string timing_only;  // ",name,name," filter of tbdk_timing_select ("" = all)
     int timing_every = 1;     // tbdk_ctx_set_option("timing_every"): events on every Nth selected launch
     std::vector<std::pair<std::string, int64_t>> timing_calls;  // selected launches per name (sampled or not)

@@ -1,5 +1,8 @@
-"""Mask clean-up and blob extraction over libtbdk (HIP, gfx950).
+"""Smoothing, thresholding, mask clean-up and blob extraction over libtbdk (HIP, gfx950).
 
+  * gaussian_blur, get_gaussian_kernel_u8 <- cv::GaussianBlur on CV_8UC1 / 8UC3 / 8UC4 (the fixed-point path,
+        modules/imgproc/src/smooth.simd.hpp: GaussianBlurFixedPoint), optionally with a threshold fused in
+  * threshold <- cv::threshold on 8-bit and CV_32FC1 images, the five plain types and THRESH_OTSU
   * get_structuring_element <- cv::getStructuringElement
   * erode, dilate, morphology_ex <- cv::erode / cv::dilate / cv::morphologyEx (MORPH_ERODE, MORPH_DILATE,
         MORPH_OPEN, MORPH_CLOSE; modules/imgproc/src/morph.dispatch.cpp), cv::cuda::createMorphologyFilter
@@ -20,6 +23,10 @@ import torch
 
 from . import _lib
 from .klt import BORDER_CONSTANT, BORDER_REFLECT, BORDER_REFLECT_101, BORDER_REPLICATE, Context, _stream_ptr  # noqa: F401
+
+BORDER_WRAP = 3  # cv::BORDER_WRAP (gaussian_blur only)
+THRESH_BINARY, THRESH_BINARY_INV, THRESH_TRUNC, THRESH_TOZERO, THRESH_TOZERO_INV = range(5)  # cv::ThresholdTypes
+THRESH_OTSU = 8
 
 MORPH_ERODE, MORPH_DILATE, MORPH_OPEN, MORPH_CLOSE = 0, 1, 2, 3  # cv::MorphTypes
 MORPH_RECT, MORPH_CROSS, MORPH_ELLIPSE = 0, 1, 2  # cv::MorphShapes
@@ -139,3 +146,73 @@ def connected_components_with_stats(image: torch.Tensor, labels: torch.Tensor | 
                                                  C.c_void_p(centroids.data_ptr()), cap, C.c_void_p(n.data_ptr()),
                                                  _stream_ptr(stream)), "tbdk_connected_components")
     return n, labels, stats, centroids
+
+
+def get_gaussian_kernel_u8(n: int, sigma: float) -> np.ndarray:
+    """the n coefficients cv::GaussianBlur uses on 8-bit images, in 1/256 units (uint16); they need not sum to 256"""
+    if int(n) < 1:
+        raise _lib.TbdkError(f"get_gaussian_kernel_u8: bad size {n}")
+    out = np.empty(int(n), np.uint16)
+    _lib.check(_lib.load().tbdk_gaussian_kernel_u8(int(n), float(sigma), out.ctypes.data_as(C.c_void_p)),
+               "tbdk_gaussian_kernel_u8")
+    return out
+
+
+def _image_layout(t: torch.Tensor, what: str, dtypes=(torch.uint8,)):
+    """(height, width, channels, pitch in bytes) of an H x W or H x W x C tensor with dense pixels and rows"""
+    if not isinstance(t, torch.Tensor) or t.dtype not in dtypes or t.dim() not in (2, 3) or t.numel() == 0:
+        raise _lib.TbdkError(f"{what}: a non-empty H x W or H x W x C tensor of {dtypes} expected")
+    h, w, cn = t.shape[0], t.shape[1], (t.shape[2] if t.dim() == 3 else 1)
+    if (t.dim() == 3 and cn > 1 and t.stride(2) != 1) or (w > 1 and t.stride(1) != cn) or \
+            (h > 1 and t.stride(0) < w * cn):
+        raise _lib.TbdkError(f"{what}: pixels and rows must be dense (a pitched view is fine)")
+    return h, w, cn, max(t.stride(0), w * cn) * t.element_size()
+
+
+def _thresh_params(threshold):
+    thresh, maxval, type_ = threshold
+    return _lib.ThreshParams(float(thresh), float(maxval), int(type_), 0)
+
+
+def gaussian_blur(src: torch.Tensor, ksize, sigmaX: float, dst: torch.Tensor | None = None, sigmaY: float = 0,
+                  borderType: int = BORDER_REFLECT_101, stream=None, threshold=None,
+                  ctx: Context | None = None) -> torch.Tensor:
+    """cv::GaussianBlur(src, dst, Size(ksize), sigmaX, sigmaY, borderType | BORDER_ISOLATED) on a uint8 H x W,
+    H x W x 3 or H x W x 4 tensor, every byte the reference's.  ksize is (width, height), each odd up to 31, or
+    <= 0 for the automatic size from sigma.  threshold (thresh, maxval, type), one of the five plain types, is
+    applied to every output byte in the same launch.  dst may be src."""
+    h, w, cn, spitch = _image_layout(src, "gaussian_blur: src")
+    if dst is None:
+        dst = torch.empty_like(src, memory_format=torch.contiguous_format)
+    dh, dw, dcn, dpitch = _image_layout(dst, "gaussian_blur: dst")
+    if (dh, dw, dcn) != (h, w, cn) or dst.device != src.device:
+        raise _lib.TbdkError("gaussian_blur: dst must have src's size, channels and device")
+    ctx = ctx or Context.get(src.device.index or 0)
+    fused = C.byref(_thresh_params(threshold)) if threshold is not None else None
+    _lib.check(ctx.lib.tbdk_gaussian_blur_u8(ctx.handle, C.c_void_p(src.data_ptr()), w, h, cn, spitch,
+                                             C.c_void_p(dst.data_ptr()), dpitch, int(ksize[0]), int(ksize[1]),
+                                             float(sigmaX), float(sigmaY), int(borderType), fused,
+                                             _stream_ptr(stream)), "tbdk_gaussian_blur_u8")
+    return dst
+
+
+def threshold(src: torch.Tensor, thresh: float, maxval: float, type: int, dst: torch.Tensor | None = None,
+              stream=None, ctx: Context | None = None):
+    """cv::threshold(src, dst, thresh, maxval, type) on a uint8 tensor of any channel count or a float32 one.
+    Returns (value, dst): value is the threshold the reference returns, a float; with THRESH_OTSU (uint8 H x W
+    only) it is a one-element int32 device tensor, written in stream order.  dst may be src."""
+    h, w, cn, spitch = _image_layout(src, "threshold: src", (torch.uint8, torch.float32))
+    if dst is None:
+        dst = torch.empty_like(src, memory_format=torch.contiguous_format)
+    dh, dw, dcn, dpitch = _image_layout(dst, "threshold: dst", (src.dtype,))
+    if (dh, dw, dcn) != (h, w, cn) or dst.device != src.device:
+        raise _lib.TbdkError("threshold: dst must have src's size, channels and device")
+    ctx = ctx or Context.get(src.device.index or 0)
+    used = C.c_double(0.0)
+    word = torch.empty(1, dtype=torch.int32, device=src.device) if int(type) & THRESH_OTSU else None
+    _lib.check(ctx.lib.tbdk_threshold(ctx.handle, C.c_void_p(src.data_ptr()), 0 if src.dtype == torch.uint8 else 2,
+                                      w, h, cn, spitch, C.c_void_p(dst.data_ptr()), dpitch, float(thresh),
+                                      float(maxval), int(type), C.byref(used),
+                                      C.c_void_p(word.data_ptr()) if word is not None else None,
+                                      _stream_ptr(stream)), "tbdk_threshold")
+    return (word if word is not None else used.value), dst

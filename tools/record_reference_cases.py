@@ -9,7 +9,8 @@ tests/_gftt_frame_cases.py; remap and warpPerspective: tests/_remap_cases.py;
 findHomography: tests/_homography_cases.py; estimateAffine2D and
 estimateAffinePartial2D: tests/_affine2d_cases.py; erode, dilate and
 morphologyEx: tests/_morph_cases.py; connectedComponentsWithStats:
-tests/_cc_cases.py)
+tests/_cc_cases.py; GaussianBlur on 8-bit images and threshold:
+tests/_blur_cases.py)
 into tests/golden/reference_<op>.npz, through tools/reference_driver.cpp (how to
 build it: tools/record_reference_cases.md).
 
@@ -21,7 +22,7 @@ child's environment only).  The driver prints checkHardwareSupport; a run whose
 flags do not show the intended state is an error, so a host without AVX2 cannot
 record.  Where the two recordings are byte-identical one copy is stored
 (state "both"); this is asserted for the pyramid, PyrLK, warpAffine, remap,
-warpPerspective, morph, cc and knn.  Where
+warpPerspective, morph, cc, knn, blur and threshold.  Where
 they differ, the state the oracle models is stored in full, and for the other
 one: whether the integer-valued results were equal (and those results where
 they were not), the share of equal 32-bit words and the largest absolute
@@ -55,6 +56,8 @@ import _mog2_cases as GC  # noqa: E402
 import _knn_cases as KC  # noqa: E402
 import _morph_cases as BC  # noqa: E402
 import _cc_cases as LC  # noqa: E402
+import _blur_cases as UC  # noqa: E402
+import _blur_oracle as UO  # noqa: E402
 
 LIMIT = 256 * 1024
 STATES = ("default", "noavx2")
@@ -63,7 +66,7 @@ MODELLED = {"pyramid": "both", "pyrlk": "both", "warpaffine": "both", "gftt": "n
             "cornermaps": "noavx2", "gftt_f32": "noavx2", "subpix": "both", "gftt_frame": "noavx2",
             "circle": "both", "remap": "both", "warpperspective": "both", "farneback": "noavx2",
             "farneback_box": "noavx2", "hog": "default", "homography": "noavx2", "affine2d": "noavx2", "mog2": "both",
-            "morph": "both", "cc": "both", "knn": "both"}
+            "morph": "both", "cc": "both", "knn": "both", "blur": "both", "threshold": "both"}
 
 
 class Driver:
@@ -498,6 +501,57 @@ def rec_cc(d):
     return cases, {}
 
 
+def rec_blur(d):
+    """GaussianBlur on the cases of tests/_blur_cases.py, and the coefficient sweep: every (n, sigma) pair's
+    response to the two impulses of the one-row sweep image (2 n bytes a pair), which determines the n 8.8
+    coefficients.  The host table's restatement is checked against every response"""
+    pairs = UC.sweep_pairs()
+    img = UC.sweep_image()
+    _, rd = d.run("blurk", dict(a=img, pairs=np.array(pairs, np.float64)), w=UC.SWEEP_W, n=len(pairs))
+    resp = rd("resp", np.uint8).reshape(len(pairs), UC.SWEEP_W)
+    rows, sums = [], []
+    for (n, sigma), r in zip(pairs, resp):
+        win = np.concatenate([r[p - n // 2:p + n // 2 + 1] for p in (UC.SWEEP_P0, UC.SWEEP_P1)])
+        keep = np.zeros(UC.SWEEP_W, bool)
+        for p in (UC.SWEEP_P0, UC.SWEEP_P1):
+            keep[p - n // 2:p + n // 2 + 1] = True
+        assert not r[~keep].any(), (n, sigma, "a response outside the kernel's reach")
+        k = UO.gaussian_kernel_u8(n, sigma)
+        assert np.array_equal(UC.sweep_response(k), win), (n, sigma, "the restated coefficients miss the response")
+        assert np.array_equal(UC.sweep_decode(win, n), k), (n, sigma)
+        rows.append(win)
+        sums.append(int(k.sum()))
+    sums = np.array(sums)
+    if d.state == "default":
+        print(f"blur: coefficient sweep of {len(pairs)} pairs: {int((sums >= 258).sum())} sum to 258 or more, "
+              f"{int((sums > 256).sum())} to more than 256, {int((sums < 256).sum())} to less; the largest sum is "
+              f"{int(sums.max())} at (n, sigma) = {pairs[int(sums.argmax())]}, the smallest {int(sums.min())}")
+    extra = dict(coef_pairs=np.array(pairs, np.float64), coef_resp=np.concatenate(rows))
+    kernels = UC.kernels()
+    cases = []
+    for c in UC.cases():
+        kw, kh, sx, sy = kernels[c["kernel"]]
+        _, rd = d.run("blur", dict(a=UC.case_image(c)), w=c["w"], h=c["h"], cn=c["cn"], kw=kw, kh=kh, sx=float(sx),
+                      sy=float(sy), border=c["border"], inplace=int(c["inplace"]))
+        shape = (c["h"], c["w"]) if c["cn"] == 1 else (c["h"], c["w"], c["cn"])
+        cases.append((dict(d=rd("d", np.uint8).reshape(shape)), {}))
+    return cases, extra
+
+
+def rec_threshold(d):
+    """threshold on the cases of tests/_blur_cases.py: the output and the returned value"""
+    cases = []
+    for c in UC.thresh_cases():
+        img = UC.thresh_image(c)
+        _, rd = d.run("threshold", dict(a=img), w=img.shape[1], h=img.shape[0], cn=1,
+                      depth="32f" if img.dtype == np.float32 else "8u", thresh=float(c["thresh"]),
+                      maxval=float(c["maxval"]), type=c["type"])
+        out = rd("d", img.dtype).reshape(img.shape)
+        ints = dict(d=out.view(np.int32) if img.dtype == np.float32 else out, t=rd("t", np.float64).view(np.int64))
+        cases.append((ints, {}))
+    return cases, {}
+
+
 def rec_farneback(d, table=None):
     cases, meta = [], []
     for w, h, ps, pn, ws, flags, use_init in table or RC.FB_CASES:
@@ -600,13 +654,14 @@ RECORDERS = {"pyramid": rec_pyramid, "pyrlk": rec_pyrlk, "gftt": rec_gftt, "gftt
              "circle": rec_circle, "warpaffine": rec_warpaffine, "remap": rec_remap,
              "warpperspective": rec_warpperspective, "farneback": rec_farneback, "farneback_box": rec_farneback_box,
              "hog": rec_hog, "homography": rec_homography, "affine2d": rec_affine2d, "mog2": rec_mog2,
-             "morph": rec_morph, "cc": rec_cc, "knn": rec_knn}
+             "morph": rec_morph, "cc": rec_cc, "knn": rec_knn, "blur": rec_blur, "threshold": rec_threshold}
 # bytes up to which an output is stored whole (tests/_reference_cases.py: WHOLE_LIMIT).  The kernels are
 # compared with the box Farneback flows within a tolerance, so all six stay whole (about 7 KB under LIMIT)
 WHOLE = {"farneback": 20480, "farneback_box": 72800, "pyrlk": 1 << 20, "gftt": 1 << 20, "gftt_mask": 1 << 20,
          "hog": 16384, "subpix": 1 << 20, "gftt_frame": 1 << 20, "remap": PC.WHOLE_LIMIT,
          "warpperspective": PC.WHOLE_LIMIT, "homography": 1 << 20, "affine2d": 1 << 20, "mog2": 1 << 20,
-         "morph": BC.WHOLE_LIMIT, "cc": 1 << 20, "knn": 1 << 20}
+         "morph": BC.WHOLE_LIMIT, "cc": 1 << 20, "knn": 1 << 20, "blur": UC.WHOLE_LIMIT,
+         "threshold": UC.WHOLE_LIMIT}
 # (gftt_f32: maps above RC.WHOLE_LIMIT as row CRCs; its corner lists are far below it)
 
 
@@ -657,6 +712,10 @@ def case_label(op, i):
         return BC.label(i)
     if op == "cc":
         return LC.label(i)
+    if op == "blur":
+        return UC.label(i)
+    if op == "threshold":
+        return UC.thresh_label(i)
     if op == "circle":
         return "centre ({}, {}) radius {}".format(*KT.CIRCLE_CASES[i])
     if op == "cornermaps":

@@ -66,6 +66,15 @@
 //                                                  connectedComponentsWithStats(a, labels, stats, centroids, conn,
 //                                                  CV_32S, type)
 //   strel shape= kw= kh= ax= ay=                   -> e (u8, kw x kh): getStructuringElement (no input image)
+//   blur  a= w= h= cn= kw= kh= sx= sy= border= inplace=0|1
+//                                                  -> d (u8): GaussianBlur(a, d, Size(kw, kh), sx, sy, border |
+//                                                  BORDER_ISOLATED); inplace=1: dst is src
+//   blurk a= w= pairs= n=                          -> resp (u8, n rows of w): the one-row image a through
+//                                                  GaussianBlur(a, d, Size(k, k), sigma) for each of the n (k, sigma)
+//                                                  pairs (f64) of the file pairs, in one process
+//   threshold a= w= h= cn= depth=8u|32f thresh= maxval= type=
+//                                                  -> d (the source's type), t (f64): threshold(a, d, thresh, maxval,
+//                                                  type) and the value it returns
 #include <cmath>
 #include <cstdio>
 #include <cstdlib>
@@ -389,8 +398,48 @@ static int run_blobs(const std::string& op, const std::string& out)
     return 0;
 }
 
+// GaussianBlur on 8-bit images, the coefficient sweep, threshold
+static int run_smooth(const std::string& op, const std::string& out)
+{
+    const int w = iarg("w");
+    if (op == "blurk") {
+        const int n = iarg("n");
+        Mat a = image("a", w, 1, 1);
+        std::vector<double> pairs((size_t)n * 2);
+        rd(arg("pairs"), pairs.data(), pairs.size() * sizeof(double));
+        Mat resp(n, w, CV_8UC1);
+        for (int i = 0; i < n; ++i) {
+            Mat d;
+            const int k = (int)pairs[2 * i];
+            GaussianBlur(a, d, Size(k, k), pairs[2 * i + 1]);
+            if (d.type() != CV_8UC1 || d.rows != 1 || d.cols != w) throw std::runtime_error("blurk: unexpected output");
+            d.copyTo(resp.row(i));
+        }
+        wr(out, "resp", resp);
+        return 0;
+    }
+    const int h = iarg("h"), cn = iarg("cn");
+    if (op == "blur") {
+        Mat a = image("a", w, h, cn), d;
+        if (iarg("inplace")) d = a;
+        const uchar* before = a.data;
+        GaussianBlur(a, d, Size(iarg("kw"), iarg("kh")), darg("sx"), darg("sy"), iarg("border") | BORDER_ISOLATED);
+        if (iarg("inplace") && d.data != before) throw std::runtime_error("the in-place call reallocated its image");
+        if (d.type() != a.type() || d.size() != a.size()) throw std::runtime_error("blur: unexpected output");
+        wr(out, "d", d);
+        return 0;
+    }
+    Mat a = image_typed("a", w, h, cn), d;
+    const double t = threshold(a, d, darg("thresh"), darg("maxval"), iarg("type"));
+    if (d.type() != a.type() || d.size() != a.size()) throw std::runtime_error("threshold: unexpected output");
+    wr(out, "d", d);
+    wr(out, "t", &t, sizeof t);
+    return 0;
+}
+
 static int run(const std::string& op, const std::string& out)
 {
+    if (op == "blur" || op == "blurk" || op == "threshold") return run_smooth(op, out);
     if (op == "morph" || op == "cc" || op == "strel") return run_blobs(op, out);
     if (op == "mog2") return run_mog2(out);
     if (op == "knn") return run_knn(out);
