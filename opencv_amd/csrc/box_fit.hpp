@@ -9,6 +9,7 @@
 #include <hip/hip_runtime.h>
 
 #include "ransac_rng.hpp"
+#include "tbdk_internal.hpp"
 
 namespace tbdk {
 
@@ -56,13 +57,6 @@ struct SimilaritySums {
 };
 
 #if defined(__HIPCC__)
-__device__ __forceinline__ double wave_sum_f64(double v)
-{
-#pragma unroll
-    for (int o = 32; o >= 1; o >>= 1) v += __shfl_xor(v, o, 64);
-    return v;
-}
-
 // Wave-parallel form: lane l sums pairs l, l+64, ... in order, then a fixed
 // xor-butterfly combines the 64 partial sums (deterministic; differs from the
 // sequential order only by double rounding, like the reference's own solve).

@@ -884,33 +884,16 @@ constexpr size_t kHogWinTileLds = 160 * 1024 - 1024;
 static hipError_t win_lds_opt_in()
 {
     static std::atomic<unsigned long long> opted{0};
-    int dev = 0;
-    hipError_t e = hipGetDevice(&dev);
-    if (e != hipSuccess) return e;
-    const unsigned long long bit = 1ull << (dev & 63);
-    if (opted.load(std::memory_order_acquire) & bit) return hipSuccess;
-    e = hipFuncSetAttribute(reinterpret_cast<const void*>(&hog_window_tile_kernel),
-                            hipFuncAttributeMaxDynamicSharedMemorySize, (int)kHogWinTileLds);
-    if (e != hipSuccess) return e;
-    opted.fetch_or(bit, std::memory_order_acq_rel);
-    return hipSuccess;
+    return lds_opt_in(opted, {reinterpret_cast<const void*>(&hog_window_tile_kernel)}, kHogWinTileLds);
 }
 
 static hipError_t tile_lds_opt_in()
 {
     static std::atomic<unsigned long long> opted{0};
-    int dev = 0;
-    hipError_t e = hipGetDevice(&dev);
-    if (e != hipSuccess) return e;
-    const unsigned long long bit = 1ull << (dev & 63);
-    if (opted.load(std::memory_order_acquire) & bit) return hipSuccess;
-    for (const void* k : {reinterpret_cast<const void*>(&hog_block_tile_kernel<true>),
-                          reinterpret_cast<const void*>(&hog_block_tile_kernel<false>)}) {
-        e = hipFuncSetAttribute(k, hipFuncAttributeMaxDynamicSharedMemorySize, (int)kHogTileLds);
-        if (e != hipSuccess) return e;
-    }
-    opted.fetch_or(bit, std::memory_order_acq_rel);
-    return hipSuccess;
+    return lds_opt_in(opted,
+                      {reinterpret_cast<const void*>(&hog_block_tile_kernel<true>),
+                       reinterpret_cast<const void*>(&hog_block_tile_kernel<false>)},
+                      kHogTileLds);
 }
 
 static hipError_t launch_blocks(HogScratch* S, const HogPlan& pl, const tbdk_hog_params* p, const float* grad,

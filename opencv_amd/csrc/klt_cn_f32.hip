@@ -17,24 +17,13 @@
 // LDS, added in column order by one lane per value.  Pyramids: interleaved fp32
 // levels with a reflect-101 frame of pad pixels, fp32 (Ix, Iy) pairs per element
 // with a zero frame (the fp32 layout of tbdk_pyr_create_f32, cn values per pixel).
-#include <atomic>
-
-#include "lk_device.hpp"
+#include "lk_walk.hpp"
 
 namespace tbdk {
 
 namespace {
 
-__device__ __forceinline__ int reflect101c(int p, int len)
-{
-    if ((unsigned)p < (unsigned)len) return p;
-    if (len == 1) return 0;
-    do {
-        if (p < 0) p = -p;
-        else p = 2 * len - 2 - p;
-    } while ((unsigned)p >= (unsigned)len);
-    return p;
-}
+using lkdev::reflect101_any;
 
 __device__ __forceinline__ float bil4(float w00, float w01, float w10, float w11, float v00, float v01, float v10,
                                       float v11, float c)
@@ -55,8 +44,8 @@ __global__ void pyr_cn_f32_copy_kernel(const uint8_t* __restrict__ src, int spit
     const int py = blockIdx.y;
     if (e >= (d.width + 2 * d.pad) * cn) return;
     const int px = e / cn, c = e - px * cn;
-    const uint8_t* srow = src + (size_t)reflect101c(py - d.pad, d.height) * spitch;
-    const int se = reflect101c(px - d.pad, d.width) * cn + c;
+    const uint8_t* srow = src + (size_t)reflect101_any(py - d.pad, d.height) * spitch;
+    const int se = reflect101_any(px - d.pad, d.width) * cn + c;
     const float v = kind == 2 ? reinterpret_cast<const float*>(srow)[se]
                               : kind == 1 ? (float)reinterpret_cast<const uint16_t*>(srow)[se] : (float)srow[se];
     reinterpret_cast<float*>(d.data + (size_t)py * d.pitch)[e] = v;
@@ -70,7 +59,7 @@ __global__ void pyr_cn_f32_down_kernel(tbdk_level s, tbdk_level d, int cn)
     const int py = blockIdx.y;
     if (e >= (d.width + 2 * d.pad) * cn) return;
     const int px = e / cn, c = e - px * cn;
-    const int rx = reflect101c(px - d.pad, d.width), ry = reflect101c(py - d.pad, d.height);
+    const int rx = reflect101_any(px - d.pad, d.width), ry = reflect101_any(py - d.pad, d.height);
     const float* s0 = reinterpret_cast<const float*>(s.data + (size_t)(2 * ry - 2 + s.pad) * s.pitch) +
                       (size_t)(s.pad + 2 * rx) * cn + c;
     float r[5];
@@ -119,32 +108,37 @@ hipError_t launch_pyr_build_f32_cn(const uint8_t* img, int pitch, int kind, cons
     return hipGetLastError();
 }
 
-// one wave per point; dynamic LDS: I, Ix, Iy of the window (winH x winW*cn each),
-// then three column-partial rows of winW*cn and three totals
-__global__ __launch_bounds__(64) void lk_cn_f32_kernel(LkArgs a)
-{
-    extern __shared__ float smem[];
-    const int i = seg_point(a, blockIdx.x);
-    if (i < 0) return;  // the whole wave
-    const int lane = threadIdx.x;
-    const int cn = a.cn, WW = a.win_w, WH = a.win_h, WE = WW * cn, AREA = WE * WH;
-    float* const iv = smem;
-    float* const gx = iv + AREA;
-    float* const gy = gx + AREA;
-    float* const col = gy + AREA;  // [3][WE]
-    float* const tot = col + 3 * WE;
-    const float FLT_SCALE = 1.f / (1 << 20);
-    const float halfx = (WW - 1) * 0.5f, halfy = (WH - 1) * 0.5f;
-    const float p0x = a.prev_pts[2 * i], p0y = a.prev_pts[2 * i + 1];
-    float outx = 0.f, outy = 0.f;
-    if (a.flags & TBDK_OPTFLOW_USE_INITIAL_FLOW) {
-        outx = a.next_pts[2 * i];
-        outy = a.next_pts[2 * i + 1];
+namespace {
+
+// the window policy of lk_walk: one wave per point; dynamic LDS: I, Ix, Iy of
+// the window (winH x winW*cn each), then three column-partial rows of winW*cn
+// and three totals
+struct CnF32Win {
+    static constexpr float FLT_SCALE = 1.f / (1 << 20);
+    const int lane, cn, WW, WH, WE, AREA;
+    float *iv, *gx, *gy, *col, *tot;
+
+    __device__ __forceinline__ CnF32Win(const LkArgs& a, float* smem, int lane_)
+        : lane(lane_), cn(a.cn), WW(a.win_w), WH(a.win_h), WE(WW * cn), AREA(WE * WH)
+    {
+        iv = smem;
+        gx = iv + AREA;
+        gy = gx + AREA;
+        col = gy + AREA;  // [3][WE]
+        tot = col + 3 * WE;
     }
-    int status = 1, nit = 0;
-    float errv = 0.f;
+
+    __device__ __forceinline__ int win_w() const { return WW; }
+    __device__ __forceinline__ int win_h() const { return WH; }
+    __device__ __forceinline__ bool gate(float fx, float fy, int ix, int iy, const LkLevel& L) const
+    {
+        return lkdev::out_of_level(fx, fy, ix, iy, WW, WH, L.w, L.h);
+    }
+    __device__ __forceinline__ void release() const { __syncthreads(); }
+
     // totals of nv column-partial rows, each added in column order by one lane
-    auto ordered_sums = [&](int nv) {
+    __device__ __forceinline__ void ordered_sums(int nv) const
+    {
         __syncthreads();
         if (lane < nv) {
             const float* q = col + lane * WE;
@@ -153,39 +147,13 @@ __global__ __launch_bounds__(64) void lk_cn_f32_kernel(LkArgs a)
             tot[lane] = t;
         }
         __syncthreads();
-    };
+    }
 
-    for (int level = a.max_level; level >= 0; --level) {
-        const LkLevel L = a.lv[level];
-        const float sc = (float)(1. / (1 << level));
-        float prevx = p0x * sc, prevy = p0y * sc, nextx, nexty;
-        if (level == a.max_level) {
-            if (a.flags & TBDK_OPTFLOW_USE_INITIAL_FLOW) {
-                nextx = outx * sc;
-                nexty = outy * sc;
-            } else {
-                nextx = prevx;
-                nexty = prevy;
-            }
-        } else {
-            nextx = outx * 2.f;
-            nexty = outy * 2.f;
-        }
-        outx = nextx;
-        outy = nexty;
-        prevx -= halfx;
-        prevy -= halfy;
-        const int ipx = (int)floorf(prevx), ipy = (int)floorf(prevy);
-        if (lkdev::out_of_level(prevx, prevy, ipx, ipy, WW, WH, L.w, L.h)) {
-            if (level == 0) {
-                status = 0;
-                errv = 0.f;
-            }
-            continue;
-        }
-        float a_ = prevx - ipx, b_ = prevy - ipy;
-        float w00 = (1.f - a_) * (1.f - b_), w01 = a_ * (1.f - b_), w10 = (1.f - a_) * b_, w11 = a_ * b_;
-        // the window's I, Ix, Iy (padded level: reflect-101 frame; derivative planes: zero frame)
+    // the window's I, Ix, Iy (padded level: reflect-101 frame; derivative planes: zero frame)
+    __device__ __forceinline__ void setup(const LkLevel& L, int ipx, int ipy, float a_, float b_, float& A11,
+                                          float& A12, float& A22) const
+    {
+        const float w00 = (1.f - a_) * (1.f - b_), w01 = a_ * (1.f - b_), w10 = (1.f - a_) * b_, w11 = a_ * b_;
         for (int k = lane; k < AREA; k += 64) {
             const int r = k / WE, e = k - r * WE;
             const int x = e / cn, c = e - x * cn;
@@ -214,101 +182,69 @@ __global__ __launch_bounds__(64) void lk_cn_f32_kernel(LkArgs a)
             col[2 * WE + e] = s2;
         }
         ordered_sums(3);
-        const float A11 = tot[0] * FLT_SCALE, A12 = tot[1] * FLT_SCALE, A22 = tot[2] * FLT_SCALE;
-        float D = A11 * A22 - A12 * A12;
-        const float minEig = (A22 + A11 - sqrtf((A11 - A22) * (A11 - A22) + 4.f * A12 * A12)) / (float)(2 * WW * WH);
-        if (a.flags & TBDK_OPTFLOW_LK_GET_MIN_EIGENVALS) errv = minEig;
-        if (minEig < a.min_eig || D < 1.19209290e-07F) {
-            if (level == 0) status = 0;
-            continue;
-        }
-        D = 1.f / D;
-        nextx -= halfx;
-        nexty -= halfy;
-        float pdx = 0.f, pdy = 0.f;
-        for (int j = 0; j < a.max_count; ++j) {
-            const int inx = (int)floorf(nextx), iny = (int)floorf(nexty);
-            if (lkdev::out_of_level(nextx, nexty, inx, iny, WW, WH, L.w, L.h)) {
-                if (level == 0) status = 0;
-                break;
-            }
-            ++nit;
-            a_ = nextx - inx;
-            b_ = nexty - iny;
-            w00 = (1.f - a_) * (1.f - b_);
-            w01 = a_ * (1.f - b_);
-            w10 = (1.f - a_) * b_;
-            w11 = a_ * b_;
-            for (int e = lane; e < WE; e += 64) {
-                const int x = e / cn, c = e - x * cn;
-                const float* q = reinterpret_cast<const float*>(L.J + (size_t)(iny + L.jpad) * L.jpitch) +
-                                 (size_t)(inx + x + L.jpad) * cn + c;
-                float bx = 0.f, by = 0.f;
-                for (int r = 0; r < WH; ++r) {
-                    const float* qn = reinterpret_cast<const float*>(reinterpret_cast<const uint8_t*>(q) + L.jpitch);
-                    const float d = bil4(w00, w01, w10, w11, q[0], q[cn], qn[0], qn[cn], -iv[r * WE + e]);
-                    bx = __builtin_fmaf(d, gx[r * WE + e], bx);
-                    by = __builtin_fmaf(d, gy[r * WE + e], by);
-                    q = qn;
-                }
-                col[e] = bx;
-                col[WE + e] = by;
-            }
-            ordered_sums(2);
-            const float b1 = tot[0] * (32.f * FLT_SCALE), b2 = tot[1] * (32.f * FLT_SCALE);
-            const float ddx = (A12 * b2 - A22 * b1) * D;
-            const float ddy = (A12 * b1 - A11 * b2) * D;
-            nextx += ddx;
-            nexty += ddy;
-            outx = nextx + halfx;
-            outy = nexty + halfy;
-            if ((double)ddx * ddx + (double)ddy * ddy <= a.eps2) break;
-            if (j > 0 && (double)fabsf(ddx + pdx) < 0.01 && (double)fabsf(ddy + pdy) < 0.01) {
-                outx -= ddx * 0.5f;
-                outy -= ddy * 0.5f;
-                break;
-            }
-            pdx = ddx;
-            pdy = ddy;
-        }
-        if (level == 0 && a.err && (a.flags & TBDK_OPTFLOW_LK_GET_MIN_EIGENVALS) == 0 && status) {
-            const float npx = outx - halfx, npy = outy - halfy;
-            const int inx = (int)floorf(npx), iny = (int)floorf(npy);
-            if (lkdev::out_of_level(npx, npy, inx, iny, WW, WH, L.w, L.h)) {
-                status = 0;
-            } else {
-                a_ = npx - inx;
-                b_ = npy - iny;
-                w00 = (1.f - a_) * (1.f - b_);
-                w01 = a_ * (1.f - b_);
-                w10 = (1.f - a_) * b_;
-                w11 = a_ * b_;
-                for (int e = lane; e < WE; e += 64) {
-                    const int x = e / cn, c = e - x * cn;
-                    const float* q = reinterpret_cast<const float*>(L.J + (size_t)(iny + L.jpad) * L.jpitch) +
-                                     (size_t)(inx + x + L.jpad) * cn + c;
-                    float ev = 0.f;
-                    for (int r = 0; r < WH; ++r) {
-                        const float* qn = reinterpret_cast<const float*>(reinterpret_cast<const uint8_t*>(q) + L.jpitch);
-                        ev += fabsf(bil4(w00, w01, w10, w11, q[0], q[cn], qn[0], qn[cn], -iv[r * WE + e]));
-                        q = qn;
-                    }
-                    col[e] = ev;
-                }
-                ordered_sums(1);
-                // lkpyramid.cpp:690: errval / (32 * winSize.width * cn * winSize.height)
-                errv = (tot[0] * 32.f) * (1.f / (float)(32 * WW * cn * WH));
-            }
-        }
-        __syncthreads();  // the window arrays are rewritten by the next level
+        A11 = tot[0] * FLT_SCALE;
+        A12 = tot[1] * FLT_SCALE;
+        A22 = tot[2] * FLT_SCALE;
     }
-    if (lane == 0) {
-        a.next_pts[2 * i] = outx;
-        a.next_pts[2 * i + 1] = outy;
-        a.status[i] = (uint8_t)status;
-        if (a.err) a.err[i] = errv;
-        if (a.iters) a.iters[i] = nit;
+
+    // element e's column of J at the window origin (inx, iny)
+    __device__ __forceinline__ const float* j_column(const LkLevel& L, int inx, int iny, int e) const
+    {
+        const int x = e / cn, c = e - x * cn;
+        return reinterpret_cast<const float*>(L.J + (size_t)(iny + L.jpad) * L.jpitch) +
+               (size_t)(inx + x + L.jpad) * cn + c;
     }
+
+    __device__ __forceinline__ void step(const LkLevel& L, int inx, int iny, float a_, float b_, float& b1,
+                                         float& b2) const
+    {
+        const float w00 = (1.f - a_) * (1.f - b_), w01 = a_ * (1.f - b_), w10 = (1.f - a_) * b_, w11 = a_ * b_;
+        for (int e = lane; e < WE; e += 64) {
+            const float* q = j_column(L, inx, iny, e);
+            float bx = 0.f, by = 0.f;
+            for (int r = 0; r < WH; ++r) {
+                const float* qn = reinterpret_cast<const float*>(reinterpret_cast<const uint8_t*>(q) + L.jpitch);
+                const float d = bil4(w00, w01, w10, w11, q[0], q[cn], qn[0], qn[cn], -iv[r * WE + e]);
+                bx = __builtin_fmaf(d, gx[r * WE + e], bx);
+                by = __builtin_fmaf(d, gy[r * WE + e], by);
+                q = qn;
+            }
+            col[e] = bx;
+            col[WE + e] = by;
+        }
+        ordered_sums(2);
+        b1 = tot[0] * (32.f * FLT_SCALE);
+        b2 = tot[1] * (32.f * FLT_SCALE);
+    }
+
+    __device__ __forceinline__ float error(const LkLevel& L, int inx, int iny, float a_, float b_) const
+    {
+        const float w00 = (1.f - a_) * (1.f - b_), w01 = a_ * (1.f - b_), w10 = (1.f - a_) * b_, w11 = a_ * b_;
+        for (int e = lane; e < WE; e += 64) {
+            const float* q = j_column(L, inx, iny, e);
+            float ev = 0.f;
+            for (int r = 0; r < WH; ++r) {
+                const float* qn = reinterpret_cast<const float*>(reinterpret_cast<const uint8_t*>(q) + L.jpitch);
+                ev += fabsf(bil4(w00, w01, w10, w11, q[0], q[cn], qn[0], qn[cn], -iv[r * WE + e]));
+                q = qn;
+            }
+            col[e] = ev;
+        }
+        ordered_sums(1);
+        // lkpyramid.cpp:690: errval / (32 * winSize.width * cn * winSize.height)
+        return (tot[0] * 32.f) * (1.f / (float)(32 * WW * cn * WH));
+    }
+};
+
+}  // namespace
+
+__global__ __launch_bounds__(64) void lk_cn_f32_kernel(LkArgs a)
+{
+    extern __shared__ float smem[];
+    const int i = seg_point(a, blockIdx.x);
+    if (i < 0) return;  // the whole wave
+    CnF32Win win(a, smem, threadIdx.x);
+    lk_walk_point(a, i, threadIdx.x == 0, win);
 }
 
 size_t lk_cn_f32_smem_bytes(int win_w, int win_h, int cn)
@@ -321,15 +257,9 @@ hipError_t launch_lk_cn_f32(const LkArgs& a, hipStream_t s)
 {
     const size_t smem = lk_cn_f32_smem_bytes(a.win_w, a.win_h, a.cn);
     static std::atomic<unsigned long long> opted{0};
-    int dev = 0;
-    hipError_t e = hipGetDevice(&dev);
-    if (e != hipSuccess) return e;
-    const unsigned long long bit = 1ull << (dev & 63);
-    if (smem > 64 * 1024 && !(opted.load(std::memory_order_acquire) & bit)) {
-        e = hipFuncSetAttribute(reinterpret_cast<const void*>(&lk_cn_f32_kernel),
-                                hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024);
+    if (smem > 64 * 1024) {
+        const hipError_t e = lds_opt_in(opted, {reinterpret_cast<const void*>(&lk_cn_f32_kernel)}, 160 * 1024);
         if (e != hipSuccess) return e;
-        opted.fetch_or(bit, std::memory_order_acq_rel);
     }
     hipLaunchKernelGGL(lk_cn_f32_kernel, dim3(a.n), dim3(64), smem, s, a);
     return hipGetLastError();

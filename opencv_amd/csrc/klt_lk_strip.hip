@@ -18,7 +18,8 @@
 //     convergence the Newton steps are sub-pixel, so most iterations are pure VALU);
 //   * G / b sums: DPP over 8-lane groups in int32 (cannot overflow), eight
 //     v_readlane into SGPRs, int64 scalar sum -> exact, wave-uniform.
-#include "lk_device.hpp"
+// The level walk is lk_walk.hpp; this file is its window policy.
+#include "lk_walk.hpp"
 
 namespace tbdk {
 
@@ -61,199 +62,140 @@ __device__ __forceinline__ void wave_sum_exact(int (&v)[N], long long (&out)[N])
     }
 }
 
+// the window policy of lk_walk: lane = one window column x of column group
+// grp, a strip of R patch rows from row0, everything in registers
+template <int WW, int WH>
+struct StripWin {
+    static constexpr int G = 64 / WW;           // column groups per wave
+    static constexpr int R = (WH + G - 1) / G;  // patch rows per lane
+    static constexpr int GRP = R <= 4 ? 16 : (R <= 8 ? 8 : 4);  // exact-reduction group (see wave_sum_exact)
+    static constexpr float FLT_SCALE = 1.f / (1 << 20);
+    int x, row0, nrows;
+    __amdgpu_buffer_rsrc_t rJ;
+    int ival[R], gx[R], gy[R];
+    // the J strip at integer origin (pinx, piny), kept while the origin stays
+    uint32_t jp[R + 1];
+    int pinx, piny;
+
+    __device__ __forceinline__ explicit StripWin(int lane)
+    {
+        const int grp = lane / WW;
+        const bool lane_on = grp < G;
+        x = lane - grp * WW;
+        row0 = lane_on ? grp * R : 0;
+        nrows = lane_on ? (WH - row0 < R ? WH - row0 : R) : 0;
+    }
+
+    static __device__ __forceinline__ constexpr int win_w() { return WW; }
+    static __device__ __forceinline__ constexpr int win_h() { return WH; }
+    static __device__ __forceinline__ bool gate(float, float, int ix, int iy, const LkLevel& L)
+    {
+        return out_of_level(ix, iy, WW, WH, L.w, L.h);
+    }
+    static __device__ __forceinline__ void release() {}
+
+    __device__ __forceinline__ void load_j(const LkLevel& L, int inx, int iny, uint32_t (&p)[R + 1]) const
+    {
+        const uint32_t joff = (uint32_t)((iny + row0 + L.jpad) * L.jpitch + inx + x + L.jpad);
+#pragma unroll
+        for (int r = 0; r <= R; ++r) p[r] = load_pair_u8_ua(rJ, joff, r * L.jpitch);
+    }
+
+    // I strip (2 columns) and derivative strip (2 columns), R + 1 rows
+    __device__ __forceinline__ void setup(const LkLevel& L, int ipx, int ipy, float fa, float fb, float& A11,
+                                          float& A12, float& A22)
+    {
+        uint32_t w0, w1;
+        bilinear_weights(fa, fb, w0, w1);
+        const __amdgpu_buffer_rsrc_t rI = make_rsrc(L.I, L.ipitch * (L.h + 2 * L.ipad) + 256);
+        const __amdgpu_buffer_rsrc_t rD = make_rsrc(L.D, L.dpitch * (L.h + 2 * L.dpad) + 256);
+        rJ = make_rsrc(L.J, L.jpitch * (L.h + 2 * L.jpad) + 256);
+        const uint32_t ioff = (uint32_t)((ipy + row0 + L.ipad) * L.ipitch + ipx + x + L.ipad);
+        const uint32_t doff = (uint32_t)((ipy + row0 + L.dpad) * L.dpitch + (ipx + x + L.dpad) * 4);
+        uint32_t ip[R + 1], dxp[R + 1], dyp[R + 1];
+#pragma unroll
+        for (int r = 0; r <= R; ++r) {
+            ip[r] = load_pair_u8_ua(rI, ioff, r * L.ipitch);
+            const uint32_t d0 = __builtin_amdgcn_raw_buffer_load_b32(rD, doff, r * L.dpitch, 0);
+            const uint32_t d1 = __builtin_amdgcn_raw_buffer_load_b32(rD, doff + 4, r * L.dpitch, 0);
+            dxp[r] = __builtin_amdgcn_perm(d1, d0, 0x05040100u);  // (Ix(x), Ix(x+1))
+            dyp[r] = __builtin_amdgcn_perm(d1, d0, 0x07060302u);  // (Iy(x), Iy(x+1))
+        }
+        int acc[3] = {0, 0, 0};
+#pragma unroll
+        for (int r = 0; r < R; ++r) {
+            const bool on = r < nrows;
+            ival[r] = bilin(ip[r], ip[r + 1], w0, w1, W_BITS1 - 5);
+            const int ix = bilin(dxp[r], dxp[r + 1], w0, w1, W_BITS1);
+            const int iy = bilin(dyp[r], dyp[r + 1], w0, w1, W_BITS1);
+            gx[r] = on ? ix : 0;
+            gy[r] = on ? iy : 0;
+            acc[0] += gx[r] * gx[r];
+            acc[1] += gx[r] * gy[r];
+            acc[2] += gy[r] * gy[r];
+        }
+        long long s[3];
+        wave_sum_exact<GRP, 3>(acc, s);
+        A11 = (float)s[0] * FLT_SCALE;
+        A12 = (float)s[1] * FLT_SCALE;
+        A22 = (float)s[2] * FLT_SCALE;
+        pinx = 0x7fffffff, piny = 0;
+#pragma unroll
+        for (int r = 0; r <= R; ++r) jp[r] = 0;
+    }
+
+    __device__ __forceinline__ void step(const LkLevel& L, int inx, int iny, float fa, float fb, float& fb1,
+                                         float& fb2)
+    {
+        if (inx != pinx || iny != piny) {  // uniform: reload the J strip
+            load_j(L, inx, iny, jp);
+            pinx = inx;
+            piny = iny;
+        }
+        uint32_t w0, w1;
+        bilinear_weights(fa, fb, w0, w1);
+        int b[2] = {0, 0};
+#pragma unroll
+        for (int r = 0; r < R; ++r) {
+            const int diff = bilin(jp[r], jp[r + 1], w0, w1, W_BITS1 - 5) - ival[r];
+            b[0] += diff * gx[r];
+            b[1] += diff * gy[r];
+        }
+        long long sb[2];
+        wave_sum_exact<GRP, 2>(b, sb);
+        fb1 = (float)sb[0] * FLT_SCALE;
+        fb2 = (float)sb[1] * FLT_SCALE;
+    }
+
+    __device__ __forceinline__ float error(const LkLevel& L, int inx, int iny, float fa, float fb) const
+    {
+        uint32_t w0, w1;
+        bilinear_weights(fa, fb, w0, w1);
+        uint32_t je[R + 1];
+        load_j(L, inx, iny, je);
+        int e[1] = {0};
+#pragma unroll
+        for (int r = 0; r < R; ++r) {
+            const int diff = bilin(je[r], je[r + 1], w0, w1, W_BITS1 - 5) - ival[r];
+            e[0] += r < nrows ? (diff < 0 ? -diff : diff) : 0;
+        }
+        long long se[1];
+        wave_sum_exact<GRP, 1>(e, se);
+        const float errval = (float)se[0];
+        return errval * 1.f / (float)(32 * WW * WH);
+    }
+};
+
 }  // namespace
 
 template <int WW, int WH>
 __global__ __launch_bounds__(256) void lk_strip_kernel(LkArgs a)
 {
-    constexpr int G = 64 / WW;           // column groups per wave
-    constexpr int R = (WH + G - 1) / G;  // patch rows per lane
-    constexpr int GRP = R <= 4 ? 16 : (R <= 8 ? 8 : 4);  // exact-reduction group (see wave_sum_exact)
     const int lane = threadIdx.x & 63;
     const int i = seg_point(a, xcd_swizzle(blockIdx.x, gridDim.x) * 4 + (threadIdx.x >> 6));
     if (i < 0) return;  // wave-uniform
-
-    const int grp = lane / WW;
-    const int x = lane - grp * WW;
-    const bool lane_on = grp < G;
-    const int row0 = lane_on ? grp * R : 0;
-    const int nrows = lane_on ? (WH - row0 < R ? WH - row0 : R) : 0;
-
-    const float FLT_SCALE = 1.f / (1 << 20);
-    const float halfx = (WW - 1) * 0.5f, halfy = (WH - 1) * 0.5f;
-    const float p0x = a.prev_pts[2 * i], p0y = a.prev_pts[2 * i + 1];
-    float outx = 0.f, outy = 0.f;
-    if (a.flags & TBDK_OPTFLOW_USE_INITIAL_FLOW) {
-        outx = a.next_pts[2 * i];
-        outy = a.next_pts[2 * i + 1];
-    }
-    int status = 1, nit = 0;
-    float errv = 0.f;
-
-    for (int level = a.max_level; level >= 0; --level) {
-        const LkLevel L = a.lv[level];
-        const float sc = (float)(1. / (1 << level));
-        float prevx = p0x * sc, prevy = p0y * sc;
-        float nextx, nexty;
-        if (level == a.max_level) {
-            if (a.flags & TBDK_OPTFLOW_USE_INITIAL_FLOW) {
-                nextx = outx * sc;
-                nexty = outy * sc;
-            } else {
-                nextx = prevx;
-                nexty = prevy;
-            }
-        } else {
-            nextx = outx * 2.f;
-            nexty = outy * 2.f;
-        }
-        outx = nextx;
-        outy = nexty;
-
-        prevx -= halfx;
-        prevy -= halfy;
-        const int ipx = (int)floorf(prevx), ipy = (int)floorf(prevy);
-        if (ipx < -WW || ipx >= L.w || ipy < -WH || ipy >= L.h) {
-            if (level == 0) {
-                status = 0;
-                errv = 0.f;
-            }
-            continue;
-        }
-        uint32_t w0, w1;
-        bilinear_weights(prevx - ipx, prevy - ipy, w0, w1);
-
-        const int hp = L.h + 2 * L.ipad;
-        const __amdgpu_buffer_rsrc_t rI = make_rsrc(L.I, L.ipitch * hp + 256);
-        const __amdgpu_buffer_rsrc_t rD = make_rsrc(L.D, L.dpitch * (L.h + 2 * L.dpad) + 256);
-        const __amdgpu_buffer_rsrc_t rJ = make_rsrc(L.J, L.jpitch * (L.h + 2 * L.jpad) + 256);
-
-        // ---- I strip (2 columns) and derivative strip (2 columns), R+1 rows
-        int ival[R], gx[R], gy[R];
-        {
-            const uint32_t ioff = (uint32_t)((ipy + row0 + L.ipad) * L.ipitch + ipx + x + L.ipad);
-            const uint32_t doff = (uint32_t)((ipy + row0 + L.dpad) * L.dpitch + (ipx + x + L.dpad) * 4);
-            uint32_t ip[R + 1], dxp[R + 1], dyp[R + 1];
-#pragma unroll
-            for (int r = 0; r <= R; ++r) {
-                ip[r] = load_pair_u8_ua(rI, ioff, r * L.ipitch);
-                const uint32_t d0 = __builtin_amdgcn_raw_buffer_load_b32(rD, doff, r * L.dpitch, 0);
-                const uint32_t d1 = __builtin_amdgcn_raw_buffer_load_b32(rD, doff + 4, r * L.dpitch, 0);
-                dxp[r] = __builtin_amdgcn_perm(d1, d0, 0x05040100u);  // (Ix(x), Ix(x+1))
-                dyp[r] = __builtin_amdgcn_perm(d1, d0, 0x07060302u);  // (Iy(x), Iy(x+1))
-            }
-            int acc[3] = {0, 0, 0};
-#pragma unroll
-            for (int r = 0; r < R; ++r) {
-                const bool on = r < nrows;
-                ival[r] = bilin(ip[r], ip[r + 1], w0, w1, W_BITS1 - 5);
-                const int ix = bilin(dxp[r], dxp[r + 1], w0, w1, W_BITS1);
-                const int iy = bilin(dyp[r], dyp[r + 1], w0, w1, W_BITS1);
-                gx[r] = on ? ix : 0;
-                gy[r] = on ? iy : 0;
-                acc[0] += gx[r] * gx[r];
-                acc[1] += gx[r] * gy[r];
-                acc[2] += gy[r] * gy[r];
-            }
-            long long s[3];
-            wave_sum_exact<GRP, 3>(acc, s);
-            // A = float(exact sum) * 2^-20   (lkpyramid.cpp:438-440)
-            const float A11 = (float)s[0] * FLT_SCALE;
-            const float A12 = (float)s[1] * FLT_SCALE;
-            const float A22 = (float)s[2] * FLT_SCALE;
-
-            float D = A11 * A22 - A12 * A12;
-            const float minEig =
-                (A22 + A11 - sqrtf((A11 - A22) * (A11 - A22) + 4.f * A12 * A12)) / (float)(2 * WW * WH);
-            if (a.flags & TBDK_OPTFLOW_LK_GET_MIN_EIGENVALS) errv = minEig;
-            if (minEig < a.min_eig || D < 1.19209290e-07F /*FLT_EPSILON*/) {
-                if (level == 0) status = 0;
-                continue;
-            }
-            D = 1.f / D;
-
-            nextx -= halfx;
-            nexty -= halfy;
-            float pdx = 0.f, pdy = 0.f;
-            int pinx = 0x7fffffff, piny = 0;
-            uint32_t jp[R + 1];
-#pragma unroll
-            for (int r = 0; r <= R; ++r) jp[r] = 0;
-            for (int j = 0; j < a.max_count; ++j) {
-                const int inx = (int)floorf(nextx), iny = (int)floorf(nexty);
-                if (inx < -WW || inx >= L.w || iny < -WH || iny >= L.h) {
-                    if (level == 0) status = 0;
-                    break;
-                }
-                nit++;
-                if (inx != pinx || iny != piny) {  // uniform: reload the J strip
-                    const uint32_t joff = (uint32_t)((iny + row0 + L.jpad) * L.jpitch + inx + x + L.jpad);
-#pragma unroll
-                    for (int r = 0; r <= R; ++r) jp[r] = load_pair_u8_ua(rJ, joff, r * L.jpitch);
-                    pinx = inx;
-                    piny = iny;
-                }
-                bilinear_weights(nextx - inx, nexty - iny, w0, w1);
-                int b[2] = {0, 0};
-#pragma unroll
-                for (int r = 0; r < R; ++r) {
-                    const int diff = bilin(jp[r], jp[r + 1], w0, w1, W_BITS1 - 5) - ival[r];
-                    b[0] += diff * gx[r];
-                    b[1] += diff * gy[r];
-                }
-                long long sb[2];
-                wave_sum_exact<GRP, 2>(b, sb);
-                const float fb1 = (float)sb[0] * FLT_SCALE;
-                const float fb2 = (float)sb[1] * FLT_SCALE;
-                const float ddx = (A12 * fb2 - A22 * fb1) * D;
-                const float ddy = (A12 * fb1 - A11 * fb2) * D;
-                nextx += ddx;
-                nexty += ddy;
-                outx = nextx + halfx;
-                outy = nexty + halfy;
-                if ((double)ddx * ddx + (double)ddy * ddy <= a.eps2) break;
-                if (j > 0 && (double)fabsf(ddx + pdx) < 0.01 && (double)fabsf(ddy + pdy) < 0.01) {
-                    outx -= ddx * 0.5f;
-                    outy -= ddy * 0.5f;
-                    break;
-                }
-                pdx = ddx;
-                pdy = ddy;
-            }
-        }
-
-        if (level == 0 && status && a.err && (a.flags & TBDK_OPTFLOW_LK_GET_MIN_EIGENVALS) == 0) {
-            const float npx = outx - halfx, npy = outy - halfy;
-            const int inx = (int)floorf(npx), iny = (int)floorf(npy);
-            if (inx < -WW || inx >= L.w || iny < -WH || iny >= L.h) {
-                status = 0;
-            } else {
-                bilinear_weights(npx - inx, npy - iny, w0, w1);
-                const uint32_t joff = (uint32_t)((iny + row0 + L.jpad) * L.jpitch + inx + x + L.jpad);
-                uint32_t jp[R + 1];
-#pragma unroll
-                for (int r = 0; r <= R; ++r) jp[r] = load_pair_u8_ua(rJ, joff, r * L.jpitch);
-                int e[1] = {0};
-#pragma unroll
-                for (int r = 0; r < R; ++r) {
-                    const int diff = bilin(jp[r], jp[r + 1], w0, w1, W_BITS1 - 5) - ival[r];
-                    e[0] += r < nrows ? (diff < 0 ? -diff : diff) : 0;
-                }
-                long long se[1];
-                wave_sum_exact<GRP, 1>(e, se);
-                const float errval = (float)se[0];
-                errv = errval * 1.f / (float)(32 * WW * WH);
-            }
-        }
-    }
-
-    if (lane == 0) {
-        a.next_pts[2 * i] = outx;
-        a.next_pts[2 * i + 1] = outy;
-        a.status[i] = (uint8_t)status;
-        if (a.err) a.err[i] = errv;
-        if (a.iters) a.iters[i] = nit;
-    }
+    StripWin<WW, WH> win(lane);
+    lk_walk_point(a, i, lane == 0, win);
 }
 
 #define TBDK_STRIP_WINDOWS(X) X(7) X(9) X(11) X(13) X(15) X(17) X(19) X(21) X(23) X(25) X(27) X(29) X(31)

@@ -1,7 +1,10 @@
-// lk_device.hpp — device helpers shared by the register-resident PyrLK kernels
-// (klt_lk_strip.hip, klt_lk_multi.hip): fixed-point bilinear weights and dot
+// lk_device.hpp — device helpers shared by the PyrLK kernels and the pyramid
+// kernels of their translation units: fixed-point bilinear weights and dot
 // products in the reference's integer arithmetic (LKTrackerInvoker,
-// video/src/lkpyramid.cpp:227-303), buffer loads of packed pixel pairs.
+// video/src/lkpyramid.cpp:227-303), buffer loads of packed pixel pairs for the
+// register-resident kernels (klt_lk_strip.hip, klt_lk_multi.hip, klt_f16.hip,
+// klt_dense.hip), the bounds gates, and CV_DESCALE / reflect-101 for the
+// LDS kernels (klt_lk.hip, klt_cn.hip, klt_cn_f32.hip).
 #pragma once
 #include "tbdk_internal.hpp"
 
@@ -9,6 +12,18 @@ namespace tbdk {
 namespace lkdev {
 
 constexpr int W_BITS = 14, W_BITS1 = 14;
+
+// CV_DESCALE
+__device__ __forceinline__ int descale(int x, int n) { return (x + (1 << (n - 1))) >> n; }
+
+// iw00..iw11 = cvRound(w * 2^14), iw11 = 2^14 - the others (lkpyramid.cpp:227-234)
+__device__ __forceinline__ void bilinear_weights_int(float fa, float fb, int& iw00, int& iw01, int& iw10, int& iw11)
+{
+    iw00 = __float2int_rn((1.f - fa) * (1.f - fb) * (1 << W_BITS));
+    iw01 = __float2int_rn(fa * (1.f - fb) * (1 << W_BITS));
+    iw10 = __float2int_rn((1.f - fa) * fb * (1 << W_BITS));
+    iw11 = (1 << W_BITS) - iw00 - iw01 - iw10;
+}
 
 typedef short s16x2 __attribute__((ext_vector_type(2)));
 typedef unsigned short u16x2 __attribute__((ext_vector_type(2)));  // packed 16-bit VALU ops (v_pk_*_u16)
@@ -138,6 +153,24 @@ __device__ __forceinline__ uint32_t load_pair_refl(__amdgpu_buffer_rsrc_t rs, in
 __device__ __forceinline__ uint32_t pair_sel(uint32_t off)
 {
     return 0x0C000C00u | ((off & 3u) + (((off & 3u) + 1u) << 16));
+}
+
+// reflect-101 of p into [0, len) for any p (BORDER_REFLECT_101, looping)
+__device__ __forceinline__ int reflect101_any(int p, int len)
+{
+    if ((unsigned)p < (unsigned)len) return p;
+    if (len == 1) return 0;
+    do {
+        if (p < 0) p = -p;
+        else p = 2 * len - 2 - p;
+    } while ((unsigned)p >= (unsigned)len);
+    return p;
+}
+
+// the bounds gate of the u8 pixel paths: a window origin outside [-win, size)
+__device__ __forceinline__ bool out_of_level(int ix, int iy, int ww, int wh, int w, int h)
+{
+    return ix < -ww || ix >= w || iy < -wh || iy >= h;
 }
 
 // the bounds gate of the float pixel paths: a window origin (ix, iy) =

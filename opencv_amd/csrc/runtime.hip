@@ -831,7 +831,9 @@ int tbdk::lk_internal(tbdk_ctx* ctx, const tbdk_pyr* prev, const tbdk_pyr* next,
         return map_err(e);
     }
     // auto: several points per wave when the window has an instantiation, else the
-    // one-point-per-wave strip kernel, else the generic LDS kernel (no derivative planes)
+    // generic LDS kernel (no derivative planes).  The one-point-per-wave strip
+    // kernel has instances for the same windows, so it runs only when asked
+    // for (impl / lk_impl 1)
     if (p->impl < 0 || p->impl > 3) return TBDK_EINVAL;
     if (cn > 1 && f32) {  // multi-channel 16U / 32F frames: the fp32 cn kernel (klt_cn_f32.hip)
         if (p->impl != 0 || !have_d || lk_cn_f32_smem_bytes(p->win_w, p->win_h, cn) > 160 * 1024) return TBDK_EINVAL;

@@ -4,6 +4,7 @@
 #include <hip/hip_runtime.h>
 
 #include <atomic>
+#include <initializer_list>
 #include <mutex>
 #include <string>
 #include <vector>
@@ -22,6 +23,15 @@ __device__ __forceinline__ int xcd_swizzle(int orig, int nwg)
 {
     const int q = nwg / 8, r = nwg % 8, xcd = orig % 8;
     return (xcd < r ? xcd * (q + 1) : r * (q + 1) + (xcd - r) * q) + orig / 8;
+}
+
+// wave-wide sum of a double by a fixed xor butterfly: the same value on every
+// lane; exact while the lane values are integers and the total is below 2^53
+__device__ __forceinline__ double wave_sum_f64(double v)
+{
+#pragma unroll
+    for (int o = 32; o >= 1; o >>= 1) v += __shfl_xor(v, o, 64);
+    return v;
 }
 
 // Border width of every padded level: >= win + 1 so the LK window plus its
@@ -52,6 +62,24 @@ struct DeviceGuard {
         if (prev >= 0 && hipGetDevice(&cur) == hipSuccess && cur != prev) (void)hipSetDevice(prev);
     }
 };
+
+// Kernels that take more than 64 KiB of dynamic LDS opt in to `bytes` of it,
+// once per device; `opted` is the caller's bitmask of devices already done.
+inline hipError_t lds_opt_in(std::atomic<unsigned long long>& opted, std::initializer_list<const void*> kernels,
+                             size_t bytes)
+{
+    int dev = 0;
+    hipError_t e = hipGetDevice(&dev);
+    if (e != hipSuccess) return e;
+    const unsigned long long bit = 1ull << (dev & 63);
+    if (opted.load(std::memory_order_acquire) & bit) return hipSuccess;
+    for (const void* k : kernels) {
+        e = hipFuncSetAttribute(k, hipFuncAttributeMaxDynamicSharedMemorySize, (int)bytes);
+        if (e != hipSuccess) return e;
+    }
+    opted.fetch_or(bit, std::memory_order_acq_rel);
+    return hipSuccess;
+}
 
 struct FbScratch;  // farneback.hip
 // GFTT scratch: one per context (the standalone calls) and one per TBD loop,
